@@ -15,6 +15,13 @@ JSON line; the default is the headline).  `--layers-total L` shards an L-layer m
 ranks instead (strong scaling, global layer indices; e.g. cfg4: h2o_l2, 32 layers over 8 GPUs);
 the `cfg4-*` / `cfg5-*` workloads default to that 32-layer split.  `--dry-run` runs the launch,
 timing and reporting harness on CPU with gloo and a stand-in step (tests/test_bench_launch.py).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes
+runs of its own: the per-kernel pass and the roofline figures (`roofline`, `path_roofline`,
+`kernel_ms_per_step`) and, for the fix_size_l2 workloads at N=1, the CPU baseline and the
+PPL-delta leg (`--no-cpu-baseline` leaves those two out).  `--dump-outputs DIR` writes what the
+last timed step returned as DIR/layer<global id>_{k,v}.npy (float32; a seeded sample of each
+tensor when the whole output is over the size budget), for comparing two builds.
 """
 import argparse
 import json
@@ -234,9 +241,10 @@ def ppl_delta(device, arch="pythia-2.8b", tokens=2000, fix=512, keep_ratio=0.5):
                       f"({dt:.0f} s)"}
 
 
-def timed_steps(step, steps, warmup, dist, sync, device, on_start=None):
+def timed_steps(step, steps, warmup, dist, sync, device, on_start=None, last=None):
     """W untimed warmup steps, then exactly K timed steps bracketed by barrier + sync on both
-    sides; returns the MAX elapsed seconds over ranks (all ranks return the same value)."""
+    sides; returns the MAX elapsed seconds over ranks (all ranks return the same value).  A list
+    passed as `last` receives what the last timed step returned."""
     for _ in range(warmup):
         step()
     sync()
@@ -254,6 +262,8 @@ def timed_steps(step, steps, warmup, dist, sync, device, on_start=None):
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if last is not None:
+        last.append(out)
     del out
     if dist:  # gloo on a host tensor: the harness needs no device collective
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -299,6 +309,29 @@ def dump_first_layer(dirname, rank, layer0, layers, out):
     (k, v), (ko, vo) = layers[0], out[0]
     np.savez(os.path.join(dirname, f"rank{rank}.npz"), k=bits(k), v=bits(v), k_out=bits(ko),
              v_out=bits(vo), layer=layer0, dtype=str(k.dtype))
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 over all ranks (--dump-outputs)
+
+
+def dump_outputs(dirname, layer0, out, world):
+    """--dump-outputs: the K and V a caller of the timed path receives, per layer (global id), as
+    DIR/layer<id>_k.npy / _v.npy in float32.  Outputs over DUMP_BUDGET in all are sampled: the
+    same seeded flat positions of every tensor on every run (1-D arrays)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    tensors = [(f"layer{layer0 + i:03d}_{n}", t) for i, kv in enumerate(out)
+               for n, t in zip("kv", kv)]
+    budget = DUMP_BUDGET // 4 // world  # elements of this rank
+    per = budget // max(len(tensors), 1)
+    whole = sum(t.numel() for _, t in tensors) <= budget
+    for j, (name, t) in enumerate(tensors):
+        if whole or t.numel() <= per:
+            a = t.float().cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(j).choice(t.numel(), per, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port():
@@ -349,7 +382,14 @@ def main():
                          "default: 32 layers per GPU (weak scaling)")
     ap.add_argument("--dtype", default="bf16", choices=sorted(DTYPES),
                     help="K/V storage dtype (fp16: what transformers >= 5 loads pythia as)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass, the roofline figures and (fix_size_l2, N=1) "
+                         "the CPU baseline and the PPL-delta leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's K/V outputs to "
+                         "DIR/layer<id>_{k,v}.npy (float32, sampled above the size budget)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: without the CPU baseline and the PPL-delta leg")
     ap.add_argument("--ppl-model", default="pythia-2.8b", choices=sorted(PPL_MODELS),
                     help="architecture of the random-init model of the PPL-delta leg")
     ap.add_argument("--dry-run", action="store_true",
@@ -367,6 +407,8 @@ def main():
                     help="test only (with --dry-run): rank R exits with an error after joining "
                          "the process group, before the first barrier")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -444,21 +486,28 @@ def main():
         def step():
             return fn(layers, skip_layers=[], **kwargs, **extra)
 
-        es = layers[0][0].element_size() if layers else 2
-        nbytes = job_bytes(capture_jobs(step), es)
-        # per-kernel durations come from a SECOND pass of K steps after the timed one: the engine
-        # then splits each launch into its kernels with HIP events recorded on the stream they
-        # run on (created with hipEventDisableSystemFence).  The timed pass itself runs exactly
-        # the untimed call (no events, no split launches).
-        timer = _engine.PhaseTimer(fenceless=True)
-    elapsed = timed_steps(step, args.steps, args.warmup, dist, sync, dev)
+        if args.full:
+            es = layers[0][0].element_size() if layers else 2
+            nbytes = job_bytes(capture_jobs(step), es)
+        # --full: per-kernel durations come from a SECOND pass of K steps after the timed one:
+        # the engine then splits each launch into its kernels with HIP events recorded on the
+        # stream they run on (created with hipEventDisableSystemFence).  The timed pass itself
+        # runs exactly the untimed call (no events, no split launches).
+        timer = _engine.PhaseTimer(fenceless=True) if args.full else None
+    last = []
+    elapsed = timed_steps(step, args.steps, args.warmup, dist, sync, dev, last=last)
+    out = last.pop()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, l0, out, world)
+    ev = sum(kv[0].size(2) for kv in layers) - sum(kv[0].size(2) for kv in out)  # per step
+    del out
     if timer:
         _engine.set_phase_timer(timer)
         timed_steps(step, args.steps, 0, dist, sync, dev)
         _engine.set_phase_timer(None)
         dur = {k: sum(v) / len(v) for k, v in timer.durations_ms().items()}
-    else:
-        dur = {"score": elapsed / max(args.steps, 1) * 1e3}
+    elif args.full:
+        dur = {"score": elapsed / args.steps * 1e3}
 
     # units all ranks processed: positions scored (layers x S) per step
     units = torch.tensor([n_layers * seq_len], dtype=torch.float64)
@@ -468,14 +517,6 @@ def main():
 
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
-        kern = max(dur, key=dur.get)  # dominant kernel of the step
-        kern_gbps = nbytes[kern] / (dur[kern] * 1e-3) / 1e9
-        headline = args.workload == HEADLINE
-        traffic = (pmc_traffic() if headline and kern == "score" and args.dtype == "bf16"
-                   and not args.dry_run else None)
-        path_gbps = nbytes["path"] * world / (ms_step * 1e-3) / 1e9
-        desc = {"score": "score_kernel (key L2 norms)",
-                "select+gather": "select_gather_kernel (selection + segment copy)"}[kern]
         cfg_kw = ", ".join(f"{k}={v!r}" for k, v in kwargs.items())
         res = {
             "metric": "KV tokens scored+evicted/sec at S=16384, fix_size=512; PPL delta vs ref",
@@ -497,22 +538,30 @@ def main():
                        "layers_total": total, "layer_offset": l0, "seq_len": seq_len, "heads": H,
                        "head_dim": head_dim,
                        "parallelism": f"layers sharded x{world}, no collectives"},
-            "roofline": {"bound": "hbm", "kernel": desc,
-                         "achieved": kern_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                         "frac": kern_gbps / PEAK_HBM_GBPS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": nbytes[kern],
-                         "traffic_source": (PMC_FILE + " (rocprofv3 --pmc)") if traffic else None},
-            "path_roofline": {"achieved": path_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                              "frac": path_gbps / PEAK_HBM_GBPS,
-                              "bytes_per_step_per_gpu": nbytes["path"]},
-            "kernel_ms_per_step": dur,
-            "tokens_evicted_per_sec": None,
+            "tokens_evicted_per_sec": ev * world * args.steps / elapsed,
         }
-        ev = sum(kv[0].size(2) for kv in layers) - sum(kv[0].size(2) for kv in step())
+        if args.full:
+            kern = max(dur, key=dur.get)  # dominant kernel of the step
+            kern_gbps = nbytes[kern] / (dur[kern] * 1e-3) / 1e9
+            headline = args.workload == HEADLINE
+            traffic = (pmc_traffic() if headline and kern == "score" and args.dtype == "bf16"
+                       and not args.dry_run else None)
+            path_gbps = nbytes["path"] * world / (ms_step * 1e-3) / 1e9
+            desc = {"score": "score_kernel (key L2 norms)",
+                    "select+gather": "select_gather_kernel (selection + segment copy)"}[kern]
+            res["roofline"] = {"bound": "hbm", "kernel": desc,
+                               "achieved": kern_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                               "frac": kern_gbps / PEAK_HBM_GBPS, "traffic": traffic,
+                               "algorithmic_bytes_per_launch": nbytes[kern],
+                               "traffic_source": (PMC_FILE + " (rocprofv3 --pmc)") if traffic
+                               else None}
+            res["path_roofline"] = {"achieved": path_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                                    "frac": path_gbps / PEAK_HBM_GBPS,
+                                    "bytes_per_step_per_gpu": nbytes["path"]}
+            res["kernel_ms_per_step"] = dur
     if args.dump_layer and not args.dry_run:
         dump_first_layer(args.dump_layer, rank, l0, layers, step())
     if rank == 0:
-        res["tokens_evicted_per_sec"] = ev * world * args.steps / elapsed
         from kvcompress import _engine as _E
         if _E.tie_policy != "reference":  # KVC_TIE_POLICY=stable: not the reference's tie order
             res["config"]["tie_policy"] = _E.tie_policy
@@ -521,7 +570,8 @@ def main():
             res["n_gpus"] = 1
         if args.dry_run:
             res["dry_run"] = True
-        elif not args.no_cpu_baseline and method == "fix_size_l2" and world == 1:  # N=1 only
+        elif (args.full and not args.no_cpu_baseline and method == "fix_size_l2"
+              and world == 1):  # N=1 only
             res["cpu_baseline"] = cpu_baseline(seq_len, head_dim, dtype=args.dtype)
             res["ppl_delta_vs_ref"] = ppl_delta(dev, arch=args.ppl_model)
         print(json.dumps(res), flush=True)

@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 
+import npz_parts
 import prng
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,14 +20,14 @@ def cases():
 
 @functools.lru_cache(maxsize=None)
 def positions():
-    return dict(np.load(os.path.join(HERE, "positions.npz")))
+    return npz_parts.load("positions")
 
 
 @functools.lru_cache(maxsize=None)
 def prims():
     with open(os.path.join(HERE, "prims.json")) as f:
         meta = json.load(f)
-    return meta, dict(np.load(os.path.join(HERE, "prims.npz")))
+    return meta, npz_parts.load("prims")
 
 
 def sha(a):

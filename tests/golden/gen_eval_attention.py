@@ -23,7 +23,7 @@ rounding is host-dependent: the tests that replay these runs skip on another CPU
 recovered from position-encoding values), so that another host can check the engine's
 selections against the reference's at every step where its forward reproduces the keys, and
 name the first step where it does not; and for the snapkv_lite and l2_compress runs every K
-row the model appended is kept (eval_loop_rows.npz), which replays their compress calls on the
+row the model appended is kept (eval_loop_rows.*.npz), which replays their compress calls on the
 reference's exact inputs on any host (step_digest.replay).
 """
 import importlib.util
@@ -34,14 +34,16 @@ import sys
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import npz_parts
+
+HERE =os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 
 THREADS = 8
 MAX_TOKENS = 700
 KW = dict(start_size=4, heavy_hitter_size=16, recent_size=40)
 FIELDS = ("perplexity", "accuracy", "num_tokens", "final_cache_size")
-# the method runs whose every appended K row is kept (eval_loop_rows.npz), so that another host
+# the method runs whose every appended K row is kept (eval_loop_rows.*.npz), so that another host
 # can replay their compress calls on the reference's exact keys (step_digest.replay): layers 1-2
 # (layer 0 is skipped by every run, and passed through untouched)
 ROW_METHODS = ("snapkv_lite", "l2_compress")
@@ -127,8 +129,7 @@ def main():
            "text": "TEXT * 2", "runs": {k: {f: v[f] for f in FIELDS} for k, v in runs.items()},
            "methods": methods, "steps": steps}
     json.dump(out, open(os.path.join(HERE, "eval_attention.json"), "w"), indent=1)
-    np.savez_compressed(os.path.join(HERE, "eval_loop_rows.npz"),
-                        **{f"{k}_rows": v for k, v in rows.items()})
+    npz_parts.save("eval_loop_rows", {f"{k}_rows": v for k, v in rows.items()})
     print(json.dumps(out["runs"]), json.dumps([{f: m[f] for f in FIELDS} for m in methods]))
 
 

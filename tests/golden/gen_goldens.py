@@ -4,16 +4,17 @@
         python tests/golden/gen_goldens.py [--prims-only | --append]
 
 --append runs only the cases added after the last generation (ids are positional, so new cases
-are only ever appended) and merges them into cases.json / positions.npz; the earlier cases'
+are only ever appended) and merges them into cases.json / positions.*.npz; the earlier cases'
 definitions must be unchanged (checked).
 
 The reference is imported from /root/reference (read-only); nothing of it is copied.  Outputs
 (data only) go to tests/golden/:
   cases.json     - per case: method, kwargs, input recipe (seeds/shapes/dtype/variant), and per
                    layer the output kind (same/view/new), shapes and SHA-256 of K_out/V_out bytes
-  positions.npz  - per case/layer: source sequence position of every output row [B,H,n_out],
-                   recovered by re-running the reference with position-encoding values
-  prims.json / prims.npz - torch.norm / argsort / topk outputs on tie-heavy rows, and the
+  positions.*.npz - per case/layer: source sequence position of every output row [B,H,n_out],
+                   recovered by re-running the reference with position-encoding values (stored
+                   in parts under 1 MiB each, like the prims: npz_parts.py)
+  prims.json / prims.*.npz - torch.norm / argsort / topk outputs on tie-heavy rows, and the
                    snapkv_lite scoring tensors (max + 1e-6, scores, pooled) per dtype
 Inputs are regenerated from tests/golden/prng.py recipes (hashes stored to detect drift).
 """
@@ -28,6 +29,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import npz_parts  # noqa: E402
 import prng  # noqa: E402
 
 assert os.path.abspath(os.environ.get("PYTHONPATH", "").split(":")[0]) == "/root/reference", \
@@ -376,7 +378,7 @@ def write_prims(meta):
     sm, sa = gen_snapkv_prims()
     with open(os.path.join(HERE, "prims.json"), "w") as f:
         json.dump({"meta": meta, "prims": pm, "snapkv": sm}, f, indent=1)
-    np.savez_compressed(os.path.join(HERE, "prims.npz"), **pa, **sa)
+    npz_parts.save("prims", {**pa, **sa})
     return pm, sm
 
 
@@ -388,7 +390,7 @@ def append_new():
     for rec, c in zip(have, CASES):  # earlier definitions must be untouched
         assert rec["id"] == c["id"] and rec["kwargs"] == c["kwargs"] and \
             rec["layers"] == c["layers"], rec["id"]
-    positions = dict(np.load(os.path.join(HERE, "positions.npz")))
+    positions = npz_parts.load("positions")
     new = []
     for c in CASES[len(have):]:
         new.append(run_case(c, positions))
@@ -396,7 +398,7 @@ def append_new():
     old["cases"] = have + new
     with open(os.path.join(HERE, "cases.json"), "w") as f:
         json.dump(old, f, indent=1)
-    np.savez_compressed(os.path.join(HERE, "positions.npz"), **positions)
+    npz_parts.save("positions", positions)
     print("appended", len(new), "cases; total", len(old["cases"]))
 
 
@@ -425,7 +427,7 @@ def main():
             "generator": "tests/golden/gen_goldens.py"}
     with open(os.path.join(HERE, "cases.json"), "w") as f:
         json.dump({"meta": meta, "cases": recs}, f, indent=1)
-    np.savez_compressed(os.path.join(HERE, "positions.npz"), **positions)
+    npz_parts.save("positions", positions)
     pm, sm = write_prims(meta)
     print("wrote", len(recs), "cases,", len(positions), "position arrays,", len(pm), "prim sets,",
           len(sm), "snapkv score sets")

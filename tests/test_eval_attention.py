@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import npz_parts
 from gpu_util import to_dev, to_np
 from oracle import h2o_oracle as HO
 from step_digest import Recorder, first_divergence, replay, unpack
@@ -367,7 +368,7 @@ def test_engine_loop_selections_match_reference_steps():
 
 def _rows():
     import os
-    return np.load(os.path.join(os.path.dirname(__file__), "golden", "eval_loop_rows.npz"))
+    return npz_parts.load("eval_loop_rows")
 
 
 def _replay_case(name, fn):
@@ -384,7 +385,7 @@ def _replay_case(name, fn):
 @pytest.mark.parametrize("name", ["snapkv_lite", "l2_compress"])
 def test_oracle_replays_reference_loop_selections(name):
     """Host-independent: the reference loop's compress calls re-run from its recorded K rows
-    (eval_loop_rows.npz, no model forward) with the oracle keep, at every one of the 699 steps,
+    (eval_loop_rows.*.npz, no model forward) with the oracle keep, at every one of the 699 steps,
     the positions the reference kept."""
     from test_ppl_parity import oracle_compress as oracle_method
     got, want = _replay_case(name, oracle_method(name))

@@ -3,9 +3,9 @@
 # scripts).  Usage:  bash tools/gpu.sh STEP [STEP ...]   with STEP one of
 #   test       pytest -m gpu (the driver's parity tier)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (headline, default K/W, CPU baseline + PPL leg)   -> bench.json
-#   quick      python bench.py --steps 20 --warmup 5 --no-cpu-baseline          -> quick.json
-#   trace      rocprofv3 --kernel-trace --stats of `bench.py --steps 20 --warmup 5`, plus the
+#   bench      python bench.py --full (headline, default K/W, CPU baseline + PPL leg) -> bench.json
+#   quick      python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline   -> quick.json
+#   trace      rocprofv3 --kernel-trace --stats of `bench.py --full --steps 20 --warmup 5`, plus the
 #              idle time between engine kernels (tools/trace_gaps.py)           -> prof/, gaps.json
 #   decode     per-token decode steps (tools/decode_bench.py)                   -> decode.json
 #   workloads  every bench.py workload at N=1                                   -> workloads.jsonl
@@ -50,15 +50,15 @@ for step in "$@"; do
           || { tail -20 "$O/smoke.log"; exit 1; }
       grep smoke "$O/smoke.log" ;;
     bench)
-      timeout -k 10 500 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
+      timeout -k 10 500 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
       cat "$O/bench.json" ;;
     quick)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/quick.json" \
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/quick.json" \
           2> "$O/quick.err" || { tail "$O/quick.err"; exit 1; }
       cat "$O/quick.json" ;;
     trace)
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats \
-          --output-format csv -d "$O/prof" -o run -- python3 "$R/bench.py" --steps 20 --warmup 5 \
+          --output-format csv -d "$O/prof" -o run -- python3 "$R/bench.py" --full --steps 20 --warmup 5 \
           --no-cpu-baseline > "$O/prof.log" 2>&1 ) || { tail "$O/prof.log"; exit 1; }
       python3 tools/trace_gaps.py "$(find "$O/prof" -name '*kernel_trace.csv' | head -1)" > "$O/gaps.json" \
           && cat "$O/gaps.json" ;;
@@ -69,7 +69,7 @@ for step in "$@"; do
     workloads)
       : > "$O/workloads.jsonl"
       for w in ${WORKLOADS:-fix512-s16384 fix512-s4096 fix512-s4096-d80 streaming-s16384 h2o-s16384 snapkv-s16384 pyramid-s16384 l2-s16384 adaptive-s16384}; do
-        timeout -k 10 200 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline \
+        timeout -k 10 200 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline \
             >> "$O/workloads.jsonl" 2>> "$O/workloads.err" || { tail "$O/workloads.err"; exit 1; }
       done
       cat "$O/workloads.jsonl" ;;
@@ -77,14 +77,14 @@ for step in "$@"; do
       : > "$O/tie_ab.jsonl"
       for w in fix512-s16384 fix512-s4096 fix512-s4096-d80 h2o-s16384 snapkv-s16384 pyramid-s16384 adaptive-s16384; do
         for pol in reference stable; do
-          KVC_TIE_POLICY=$pol timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 5 \
+          KVC_TIE_POLICY=$pol timeout -k 10 300 python bench.py --full --workload $w --steps 20 --warmup 5 \
               --no-cpu-baseline > "$O/tie_one.json" 2> "$O/tie_one.err" || { tail "$O/tie_one.err"; exit 1; }
           python3 -c "import json; d=json.load(open('$O/tie_one.json')); print(json.dumps({'workload': '$w', 'policy': '$pol', 'ms_per_step': d['ms_per_step'], 'kernel_ms_per_step': d['kernel_ms_per_step']}))" >> "$O/tie_ab.jsonl"
         done
       done
       for w in cfg4-h2o-l32 cfg5-snapkv-l32 cfg5-pyramid-l32; do
         for pol in reference stable; do
-          KVC_TIE_POLICY=$pol timeout -k 10 200 python bench.py --workload $w --as-shard 7/8 --steps 50 \
+          KVC_TIE_POLICY=$pol timeout -k 10 200 python bench.py --full --workload $w --as-shard 7/8 --steps 50 \
               --warmup 5 --no-cpu-baseline > "$O/tie_one.json" 2> "$O/tie_one.err" || { tail "$O/tie_one.err"; exit 1; }
           python3 -c "import json; d=json.load(open('$O/tie_one.json')); print(json.dumps({'workload': '$w', 'shard': '7/8', 'policy': '$pol', 'ms_per_step': d['ms_per_step'], 'kernel_ms_per_step': d['kernel_ms_per_step']}))" >> "$O/tie_ab.jsonl"
         done
@@ -101,12 +101,12 @@ for step in "$@"; do
       : > "$O/shard.jsonl"
       for w in cfg4-h2o-l32 cfg5-snapkv-l32 cfg5-pyramid-l32; do
         for r in 0 7; do
-          timeout -k 10 200 python bench.py --workload $w --as-shard $r/8 --steps 50 --warmup 5 \
+          timeout -k 10 200 python bench.py --full --workload $w --as-shard $r/8 --steps 50 --warmup 5 \
               --no-cpu-baseline >> "$O/shard.jsonl" 2>> "$O/shard.err" || { tail "$O/shard.err"; exit 1; }
         done
       done
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats \
-          --output-format csv -d "$O/shardprof" -o run -- python3 "$R/bench.py" --workload cfg5-pyramid-l32 \
+          --output-format csv -d "$O/shardprof" -o run -- python3 "$R/bench.py" --full --workload cfg5-pyramid-l32 \
           --as-shard 7/8 --steps 50 --warmup 5 --no-cpu-baseline > "$O/shardprof.log" 2>&1 ) \
           || { tail "$O/shardprof.log"; exit 1; }
       python3 tools/trace_gaps.py "$(find "$O/shardprof" -name '*kernel_trace.csv' | head -1)" timed > "$O/shard_gaps.json" \
@@ -114,7 +114,7 @@ for step in "$@"; do
     dtypes)
       : > "$O/dtypes.jsonl"
       for d in fp32 fp16; do
-        timeout -k 10 200 python bench.py --dtype $d --steps 20 --warmup 5 --no-cpu-baseline \
+        timeout -k 10 200 python bench.py --full --dtype $d --steps 20 --warmup 5 --no-cpu-baseline \
             >> "$O/dtypes.jsonl" 2>> "$O/dtypes.err" || { tail "$O/dtypes.err"; exit 1; }
       done
       cat "$O/dtypes.jsonl" ;;
@@ -144,7 +144,7 @@ for step in "$@"; do
       for rep in $reps; do
         for lib in ${libs//,/ }; do
           for w in ${wls//,/ }; do
-            KVC_LIB="$LIBDIR/$lib.so" timeout -k 10 200 python bench.py --workload $w --steps 20 \
+            KVC_LIB="$LIBDIR/$lib.so" timeout -k 10 200 python bench.py --full --workload $w --steps 20 \
                 --warmup 5 --no-cpu-baseline $args > "$O/ab_one.json" 2> "$O/ab.err" || { tail "$O/ab.err"; exit 1; }
             echo "{\"recipe\": \"$name\", \"rep\": $rep, \"lib\": \"$lib\", \"workload\": \"$w\", \"args\": \"$args\", \"r\": $(cat "$O/ab_one.json")}" >> "$O/ab.jsonl"
           done
