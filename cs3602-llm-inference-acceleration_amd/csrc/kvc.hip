@@ -3422,7 +3422,8 @@ __device__ __forceinline__ void store_vec(void* base, int64_t i, int n, const fl
 constexpr int kAccCols = 8;
 template <int DT, int ODT>
 __global__ void __launch_bounds__(kColThreads)
-    attn_accum_kernel(const AttnChunk T, int H, int BH, float decay, int group, int vec_min) {
+    attn_accum_kernel(const AttnChunk T, int H, int BH, float decay, int group, int vec_min,
+                      int rnd) {
   constexpr int ESZ = DTypeTraits<DT>::esz;
   constexpr int NDT = ODT == DT ? DT : KVC_F32;  // acc_new's dtype
   constexpr int V = kAccCols;
@@ -3452,7 +3453,7 @@ __global__ void __launch_bounds__(kColThreads)
       }
       const auto ld = [&](int i) { return load_dt<DT>(a + (int64_t)i * qs, j); };
       // the accumulating store adds to the zero-filled output
-      s[e] = col_ilp(j, k, ly->col_chunk, 128 / ESZ, group, vec_min) ? 0.f + ilp4_sum(ld, q)
+      s[e] = col_ilp(j, k, ly->col_chunk, rnd, group, vec_min) ? 0.f + ilp4_sum(ld, q)
                                                                       : 0.f + cascade_sum(ld, q, 0, 1);
     }
   }
@@ -3893,8 +3894,10 @@ static int attn_params_check(const kvc_attn_params_t* p, bool accumulate = false
   // flags: KVC_ATTN_HH_STABLE (both entry points: one params struct serves a decode step's
   // accumulate and heavy-hitter calls) | kvc_attn_accumulate's KVC_ATTN_OLD_DTYPE(d), bits 0-1,
   // d a dtype other than p->dtype
+  // KVC_ATTN_SCALAR_SUM: kvc_attn_accumulate only
   const int od = p->flags & 3;
-  if ((p->flags & ~(3 | KVC_ATTN_HH_STABLE)) || (od && (!accumulate || od == KVC_ATTN_OLD_DTYPE(p->dtype))))
+  if ((p->flags & ~(3 | KVC_ATTN_HH_STABLE | (accumulate ? KVC_ATTN_SCALAR_SUM : 0))) ||
+      (od && (!accumulate || od == KVC_ATTN_OLD_DTYPE(p->dtype))))
     return KVC_E_ARG;
   if (p->vec_bytes < 16 || p->vec_bytes > 64 || p->vec_bytes % 16) return KVC_E_ARG;
   if ((int64_t)p->batch * p->heads > 0x7FFFFFFF / kArgLayers) return KVC_E_ARG;
@@ -3921,7 +3924,11 @@ static int accumulate_impl(const kvc_attn_params_t* p, const kvc_attn_layer_t* l
       return KVC_E_TOO_LONG;
   }
   const int H = p->heads, BH = p->batch * p->heads;
-  const int group = 4 * (p->vec_bytes / 4), vec_min = p->vec_bytes / es;
+  // KVC_ATTN_SCALAR_SUM (the reference summed a last-dim-strided tensor): aten's scalar outer
+  // loop -- groups of four columns in every call, thread chunk bounds not rounded
+  const bool scalar = (p->flags & KVC_ATTN_SCALAR_SUM) != 0;
+  const int group = scalar ? 4 : 4 * (p->vec_bytes / 4), vec_min = scalar ? 1 : p->vec_bytes / es;
+  const int rnd = scalar ? 1 : 128 / es;
   for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kArgLayers) {
     const int cn = nl - c0 < kArgLayers ? nl - c0 : kArgLayers;
     AttnChunk T;
@@ -3933,7 +3940,7 @@ static int accumulate_impl(const kvc_attn_params_t* p, const kvc_attn_layer_t* l
     rc = with_dtype(p->dtype, [&](auto dt) {
       return with_dtype(odt, [&](auto od) {
         return launch_k(attn_accum_kernel<decltype(dt)::value, decltype(od)::value>, grid,
-                        dim3(kColThreads), 0, s, T, H, BH, p->decay, group, vec_min);
+                        dim3(kColThreads), 0, s, T, H, BH, p->decay, group, vec_min, rnd);
       });
     });
   }

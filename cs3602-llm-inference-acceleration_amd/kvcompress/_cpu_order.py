@@ -44,7 +44,8 @@ def column_chunk(cols, outer, red, esz, nthreads):
 
 
 def attn_sum_chunk(attn, nthreads):
-    """Chunk of attn.sum(dim=2) for attn [B,H,q,k] (last dim contiguous)."""
+    """Chunk of attn.sum(dim=2) for attn [B,H,q,k] (last dim contiguous, or with a step: the
+    chunks then keep their bounds, KVC_ATTN_SCALAR_SUM)."""
     B, H, q, k = attn.shape
     if q < 2:
         return 0

@@ -23,6 +23,7 @@ DEV_SELECT_BOUNDS, DEV_INDEX_RANGE, DEV_INTERNAL = 1, 2, 4  # enum kvc_device_st
 
 
 ATTN_HH_STABLE = 4  # kvc_attn_params.flags: kvc_heavy_hitters with the stable tie order
+ATTN_SCALAR_SUM = 8  # kvc_attn_accumulate: the reference summed last-dim-strided attention
 
 
 def ATTN_OLD_DTYPE(d):

@@ -30,11 +30,14 @@ from ..utils import normalize_kv_cache
 _DT = {torch.bfloat16: N.KVC_BF16, torch.float16: N.KVC_F16, torch.float32: N.KVC_F32}
 
 
-def _attn_params(dtype, B, H, decay, device, old_dtype=None):
+def _attn_params(dtype, B, H, decay, device, old_dtype=None, scalar_sum=False):
     """old_dtype: the carried accumulations' dtype when it differs from the attention's (torch
     then promotes to float32, h2o_attention.py:129-151; kvc_attn_accumulate's
-    KVC_ATTN_OLD_DTYPE flag)."""
+    KVC_ATTN_OLD_DTYPE flag).  scalar_sum: the attention the reference sums is not last-dim
+    contiguous (KVC_ATTN_SCALAR_SUM: aten's scalar loop and its column order)."""
     flags = N.ATTN_OLD_DTYPE(_DT[old_dtype]) if old_dtype not in (None, dtype) else 0
+    if scalar_sum:
+        flags |= N.ATTN_SCALAR_SUM
     if E.tie_policy == "stable":  # the heavy hitters' selection (kvc_heavy_hitters) only
         flags |= N.ATTN_HH_STABLE
     return N.AttnParams(dtype=_DT[dtype], batch=B, heads=H, vec_bytes=CO.SUM_VEC_BYTES,
@@ -83,8 +86,8 @@ class H2OAttentionManager:
     @E.status_checked
     def update_attention_scores(self, attentions, skip_layers: List[int] = []):
         """h2o_attention.py:84-153 for every given layer in one engine launch per
-        (device, dtype, B, H, carried dtype) group: acc <- acc*decay (zero-extended to the new key
-        length; reset to zeros if the cache shrank) + attention summed over queries.  A carried
+        (device, dtype, B, H, carried dtype, last-dim step) group: acc <- acc*decay
+        (zero-extended to the new key length; reset to zeros if the cache shrank) + attention summed over queries.  A carried
         accumulation of another float dtype than the new attention is promoted as torch does
         (`acc * decay` rounded in its own dtype, the sum in float32, a float32 result: :129-151)."""
         if attentions is None:
@@ -96,11 +99,16 @@ class H2OAttentionManager:
                 continue
             b, h, q, key_len = attn.shape
             _check_gpu(attn, f"attention of layer {layer_idx}")
+            # the q-sum's thread chunks follow the attention the reference sums (:116), before
+            # any copy or broadcast below; a last dim with a step (a [..., ::2] view: rows still
+            # apart, columns not adjacent) puts torch's sum on aten's scalar loop, whose columns
+            # add in another order than the SIMD loop's: the kernel sums a contiguous copy in
+            # that order (KVC_ATTN_SCALAR_SUM)
+            chunk = CO.attn_sum_chunk(attn, threads)
+            scalar = (key_len > 1 and attn.stride(3) > 1 and
+                      (q == 1 or attn.stride(2) >= attn.stride(3) * key_len))
             if attn.stride(3) != 1 or attn.data_ptr() % attn.element_size():
                 attn = attn.contiguous()
-            # the q-sum's thread chunks follow the attention the reference sums (:116), before
-            # any broadcast below
-            chunk = CO.attn_sum_chunk(attn, threads)
             acc = self.accumulated_attention.get(layer_idx)
             old = None
             if acc is not None and acc.size(-1) <= key_len:  # decay (and zero-extend) (:124-146)
@@ -126,10 +134,11 @@ class H2OAttentionManager:
                     attn = attn.expand(b, h, q, key_len)
                 old = acc.contiguous()
             # acc.size(-1) > key_len: reset to zeros (:138-144) -- old stays None
-            key = (attn.get_device(), attn.dtype, b, h, attn.dtype if old is None else old.dtype)
+            key = (attn.get_device(), attn.dtype, b, h, attn.dtype if old is None else old.dtype,
+                   scalar)
             groups.setdefault(key, []).append((layer_idx, attn, old, chunk))
             self.current_seq_len = key_len
-        for (device, dtype, b, h, odt), jobs in groups.items():
+        for (device, dtype, b, h, odt, scalar), jobs in groups.items():
             with torch.cuda.device(device):
                 sizes = [b * h * a.size(3) for _, a, _, _ in jobs]
                 ndt = dtype if odt == dtype else torch.float32  # torch's promotion (:129-151)
@@ -141,7 +150,7 @@ class H2OAttentionManager:
                                 old.data_ptr() if old is not None else 0, acc.data_ptr(),
                                 a.size(2), a.size(3), old.size(-1) if old is not None else 0,
                                 chunk)
-                p = _attn_params(dtype, b, h, self.decay_factor, device, odt)
+                p = _attn_params(dtype, b, h, self.decay_factor, device, odt, scalar)
                 rc = N.attn_accumulate(p, table, torch.cuda.current_stream(device).cuda_stream)
                 N.check(rc, "kvc_attn_accumulate")
                 for (li, _, _, _), acc in zip(jobs, accs):

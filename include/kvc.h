@@ -117,7 +117,11 @@ enum kvc_status {
 };
 
 /* One layer.  Inputs K,V: [batch, heads, seq_len, head_dim], last dim contiguous, arbitrary
- * element strides for the other three dims.  Outputs: contiguous [batch, heads, n_out, head_dim]
+ * element strides for the other three dims, K's and V's independent of each other (16-byte
+ * multiples for every dim larger than 1, else KVC_E_ALIGN; a stride of 0 -- an expanded batch --
+ * and offsets beyond 2^32 bytes are fine).  Every kernel path is tested on such views: windows of
+ * a static cache, the K / V thirds of a fused QKV projection, permuted, sliced and expanded
+ * tensors (the test_strided_inputs suite).  Outputs: contiguous [batch, heads, n_out, head_dim]
  * with n_out = sink_len + n_select + tail_len. */
 typedef struct kvc_layer {
   const void* k;
@@ -225,7 +229,8 @@ typedef struct kvc_attn_params {
                            layer) is of enum kvc_dtype d != dtype -- the reference then promotes
                            through `acc * decay`, torch.cat and `+` (:129-151): base is rounded to
                            d, and acc_new is FLOAT32 = fp32(base) + fp32(attn.sum), unrounded --
-                           and/or KVC_ATTN_HH_STABLE, which it ignores (one struct per step) */
+                           and/or KVC_ATTN_HH_STABLE, which it ignores (one struct per step),
+                           and/or KVC_ATTN_SCALAR_SUM */
   uint32_t* device_status; /* optional, as kvc_params_t */
 } kvc_attn_params_t;
 
@@ -234,6 +239,14 @@ typedef struct kvc_attn_params {
  * descending sort of the head sums (KVC_ALGO_STABLE's tie order) instead of torch.topk's; zones
  * of at most 65 536 positions (else KVC_E_TOO_LONG). */
 #define KVC_ATTN_HH_STABLE 4
+/* kvc_attn_params.flags bit 3, kvc_attn_accumulate only (kvc_heavy_hitters refuses it): the
+ * reference summed attention tensors whose LAST dim has a step (a [..., ::2] view), and `attn`
+ * is a last-dim-contiguous copy of each.  torch's CPU sum then runs aten's
+ * scalar outer loop instead of the SIMD one: in every loop call the cascade takes whole groups of
+ * FOUR columns and row_sum the rest, and the thread chunks of col_chunk columns keep their
+ * bounds (no rounding to 128 bytes).  vec_bytes is ignored.  (Additive within ABI 4: a library
+ * without the flag refuses it with KVC_E_ARG like every unknown bit.) */
+#define KVC_ATTN_SCALAR_SUM 8
 
 /* One layer of update_attention_scores (:100-154). */
 typedef struct kvc_attn_layer {

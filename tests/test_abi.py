@@ -133,6 +133,80 @@ def test_plan_rejects_bad_layers():
     assert rc == 0
 
 
+def _strided_layer(B, H, S, D, ks=None, vs=None, k=10):
+    """A selecting layer of a [B, H, S, D] call with the given K / V element strides (contiguous
+    by default)."""
+    t = np.zeros(1, dtype=N.LAYER_DTYPE)[0]
+    t["k"] = t["v"] = t["k_out"] = t["v_out"] = 4096
+    cont = (H * S * D, S * D, D)
+    t["k_stride"] = ks or cont
+    t["v_stride"] = vs or cont
+    t["seq_len"], t["zone_start"], t["zone_len"], t["n_select"] = S, 0, S, min(k, S)
+    return t
+
+
+@pytest.mark.parametrize("dtype, es", [(N.KVC_BF16, 2), (N.KVC_F32, 4)])
+@pytest.mark.parametrize("side", ["k_stride", "v_stride"])
+@pytest.mark.parametrize("dim", [0, 1, 2])
+def test_plan_stride_alignment_rules(dim, side, dtype, es):
+    """include/kvc.h: every K / V stride of a dim larger than 1 must be a multiple of 16 bytes,
+    K and V checked separately; a dim of size 1 (batch, heads or seq_len) is never stepped over,
+    so its stride is free."""
+    B, H, S, D = 2, 3, 100, 64
+    cont = [H * S * D, S * D, D]
+    p = dict(dtype=dtype, batch=B, heads=H, head_dim=D)
+    for off in (1, 4 // es + 1, 16 // es - 1):  # 2..14 bytes off a multiple of 16
+        st = list(cont)
+        st[dim] += off
+        assert (st[dim] * es) % 16
+        t = _strided_layer(B, H, S, D, **{side[0] + "s": tuple(st)})
+        assert N.plan(_params(**p), np.array([t], dtype=N.LAYER_DTYPE))[0] == -4  # KVC_E_ALIGN
+        # the same stride on a dim of size 1 is accepted
+        shape1 = [B, H, S]
+        shape1[dim] = 1
+        B1, H1, S1 = shape1
+        t = _strided_layer(B1, H1, S1, D, **{side[0] + "s": tuple(st)})  # S1 == 1: copied whole
+        assert t["n_select"] > 0
+        p1 = dict(dtype=dtype, batch=B1, heads=H1, head_dim=D)
+        assert N.plan(_params(**p1), np.array([t], dtype=N.LAYER_DTYPE))[0] == 0, (dim, off)
+    # a multiple of 16 bytes more is fine
+    st = list(cont)
+    st[dim] += 16 // es
+    t = _strided_layer(B, H, S, D, **{side[0] + "s": tuple(st)})
+    assert N.plan(_params(**p), np.array([t], dtype=N.LAYER_DTYPE))[0] == 0
+
+
+@pytest.mark.parametrize("dtype", [N.KVC_BF16, N.KVC_F32])
+def test_plan_accepts_aligned_noncontiguous_strides(dtype):
+    """A window of a static cache, the K / V thirds of a fused QKV projection and a stride-0
+    (expanded) batch plan exactly like the contiguous table: strides are addresses, not sizes."""
+    B, H, S, D = 2, 3, 300, 64
+    p = dict(dtype=dtype, batch=B, heads=H, head_dim=D)
+    rc, want = N.plan(_params(**p), np.array([_strided_layer(B, H, S, D)], dtype=N.LAYER_DTYPE))
+    assert rc == 0
+    T = S + 37
+    triples = {"static": (H * T * D, T * D, D), "fused_qkv": (S * H * 3 * D, 3 * D, H * 3 * D),
+               "expand": (0, S * D, D)}
+    fields = [f for f, _ in N.PlanInfo._fields_]
+    for name, st in triples.items():
+        for ks, vs in ((st, None), (None, st), (st, st)):
+            table = np.array([_strided_layer(B, H, S, D, ks, vs)], dtype=N.LAYER_DTYPE)
+            rc, info = N.plan(_params(**p), table)
+            assert rc == 0, name
+            assert [getattr(info, f) for f in fields] == [getattr(want, f) for f in fields], name
+
+
+def test_plan_exempts_layers_without_output_from_alignment():
+    """A layer with n_out == 0 is never read or written: no pointer or stride rule applies."""
+    t = _strided_layer(2, 3, 100, 64, ks=(1, 3, 5), vs=(7, 9, 11))
+    t["n_select"] = 0
+    t["k"] = t["v"] = 4100
+    t["k_out"] = t["v_out"] = 0
+    assert N.plan(_params(batch=2, heads=3, head_dim=64), np.array([t], dtype=N.LAYER_DTYPE))[0] == 0
+    t["n_select"] = 10
+    assert N.plan(_params(batch=2, heads=3, head_dim=64), np.array([t], dtype=N.LAYER_DTYPE))[0] < 0
+
+
 def test_plan_long_zone_gets_global_scratch():
     """Zones longer than the LDS limit (16384) select from a per-row global scratch."""
     short = np.array([_layer(16384, 0, 16384, 512)], dtype=N.LAYER_DTYPE)
