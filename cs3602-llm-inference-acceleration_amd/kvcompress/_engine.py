@@ -291,6 +291,7 @@ def _upload(params, table, device, js, B, H):
 
 
 def _launch(params, table, ws, info, stream, phases):
+    _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
     for name, bits in steps:
@@ -381,10 +382,18 @@ def status_word(device):
     w = _status_words.get(device)
     if w is None:
         w = _status_words[device] = _new_status_word(device)
-    t = getattr(_check_state, "touched", None)
-    if t is not None:  # inside a status-checked call: this device is read at its end
-        t.add(device)
+    _touch(device)
     return w
+
+
+def _touch(device):
+    """Record a launch on `device`: inside a status-checked call (check on), the outermost call
+    reads that device's word at its end.  Every path that enqueues engine kernels calls this --
+    _launch, the native replays (kvc_host.run / run_h2o) -- not only the ones that make a word:
+    a cached plan carries its word's address in its Params and never asks for it again."""
+    t = getattr(_check_state, "touched", None)
+    if t is not None:
+        t.add(device)
 
 
 def _new_status_word(device):
@@ -452,8 +461,8 @@ def raise_on_status(devices=None):
 
 def _checked_call(call, result_devices=None):
     """Run call() as a status-checked entry point: with check_status on, the OUTERMOST such call
-    ends by reading the words of the devices its launches touched (status_word() calls during
-    the call, plus `result_devices(out)` for launches that bypass it -- the native replay).
+    ends by reading the words of the devices its launches touched (_touch() calls during the
+    call, plus `result_devices(out)`).
     No read while a CUDA graph is being captured (the read synchronises)."""
     st = _check_state
     if not check_status or getattr(st, "depth", 0) > 0:
@@ -806,6 +815,8 @@ def memoized(fn):
         rec = call_memo.get(key)
         if rec is not None:
             memo_stats["replayed"] += 1
+            if rec.n_jobs:
+                _touch(sig[4])
             if rec.n_jobs and torch.cuda.current_device() != sig[4]:
                 with torch.cuda.device(sig[4]):
                     return hm.run(kvl, rec.actions, rec.table, rec.n_jobs, rec.n_outs,

@@ -401,6 +401,7 @@ def _replay_step(kvl, attention_scores, mgr, start_size, heavy_hitter_size, rece
         step_memo.put(key, plan, int(plan.ws.numel()) + int(plan.hh_ws.numel()))
         step_stats["planned"] += 1
     step_stats["replayed"] += 1
+    E._touch(sig[4])  # the replay enqueues from cached params: no status_word() call
     with torch.cuda.device(sig[4]):
         out, acc = hm.run_h2o(
             kvl, attention_scores, accs, plan.a_layers, plan.a_table.ctypes.data,

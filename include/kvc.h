@@ -27,9 +27,22 @@
  * Phases (stream-ordered on `stream`, one kernel each per chunk of <= 64 layers; SELECT and
  * GATHER run as one select_gather kernel unless params.flags has KVC_FLAG_SPLIT_SELECT_GATHER):
  *   SCORE  : key L2 norms of every zone token           -> workspace norm region
+ *            (and per-64-token-tile statistics of those norms -> a workspace region behind the
+ *            index region that kvc_plan() sizes and kvc_plan_info_t does not name)
  *   SELECT : per (layer,b,h) row: snapkv scoring (opt.), reference-exact k-selection,
  *            ascending zone-local indices                -> workspace index region (int32)
  *   GATHER : segment copy of K and V into k_out / v_out (caller-allocated, contiguous)
+ * The phases of one call may be launched separately, in this order on one stream and one
+ * workspace (SCORE, then SELECT | GATHER; or SCORE, SELECT, GATHER): the outputs are the bytes of
+ * a KVC_PHASE_ALL launch.  A separate SELECT writes the index region (n_select ascending indices
+ * per row) even without KVC_FLAG_SPLIT_SELECT_GATHER.  No phase reads workspace bytes that an
+ * earlier phase of the call did not write, so the workspace needs no initialisation.
+ *   - SELECT of KVC_SCORE_SNAPKV rows reads SCORE's tile statistics: SCORE must have run on the
+ *     same workspace with the same table.
+ *   - SELECT of plain-norm rows (KVC_SCORE_NORM) reads the norm region only, and only columns
+ *     [0, zone_len) of a row decide its result: the caller may fill those itself (row
+ *     layer.row0 + b*heads + h, norm_row_stride elements of dtype apart) and launch SELECT
+ *     without SCORE.  Columns from zone_len up to norm_row_stride may hold anything.
  *
  * Ownership: the caller allocates outputs and the workspace; the library never allocates,
  * frees or synchronises.  Entry points are reentrant (no global mutable state, no environment
@@ -95,7 +108,11 @@ enum kvc_flag {
  * library never clears it; the caller zeroes it and reads it after the stream has drained. */
 enum kvc_device_status {
   KVC_DEV_SELECT_BOUNDS = 1, /* a selection row exceeded its kernel's zone capacity: nothing
-                                is selected and none of that row's output rows is written
+                                is selected and the row's index entries are not written.  In
+                                the fused select_gather kernel none of that row's output rows
+                                is written either; a separate GATHER kernel (SPLIT flag, long
+                                zones, separately launched phases) still copies the row's sink
+                                and tail and gathers through whatever the index row held
                                 (never expected: kvc_launch picks kernels by the planned zone
                                 lengths)                                                       */
   KVC_DEV_INDEX_RANGE = 2,   /* an external index lay outside its zone and was clamped        */

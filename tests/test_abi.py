@@ -371,6 +371,27 @@ def test_device_status_bits_match_header():
     assert all(name.split()[0] in vals for _, name in E._STATUS_BITS)
 
 
+def test_header_states_the_phase_and_bounds_contracts():
+    """include/kvc.h says what tests/test_phase_contract.py and test_device_status.py pin: SCORE
+    also writes tile statistics, snapkv SELECT needs them, plain-norm SELECT needs columns
+    [0, zone_len) only, and 'no output row written' is the fused kernel's behaviour.
+    INTEGRATION.md repeats it."""
+    hdr = " ".join(re.sub(r"\s*\n \*\s*", " ", open(os.path.join(ROOT, "include", "kvc.h"))
+                          .read()).split())
+    for text in ("per-64-token-tile statistics of those norms",
+                 "The phases of one call may be launched separately",
+                 "the workspace needs no initialisation",
+                 "SELECT of KVC_SCORE_SNAPKV rows reads SCORE's tile statistics",
+                 "only columns [0, zone_len) of a row decide its result",
+                 "In the fused select_gather kernel none of that row's output rows is written"):
+        assert text in hdr, text
+    doc = " ".join(open(os.path.join(ROOT, "INTEGRATION.md")).read().split())
+    for text in ("SCORE must have run on the same workspace",
+                 "reads only columns `[0, zone_len)` of its norm row",
+                 "the fused select_gather kernel then writes none of the row's output rows"):
+        assert text in doc, text
+
+
 def test_scored_calls_reserve_the_tile_statistics_region():
     """kvc_plan reserves rows x norm_row_stride / 64 u32 after the index region for SCORE's
     per-tile statistics (round 6): a snapkv row's tile norm maxima, a plain-norm row's level-0

@@ -79,6 +79,40 @@ def test_state_reset_after_an_exception(reads):
     assert reads == [{4}]
 
 
+def test_launch_with_cached_params_is_read(reads, monkeypatch):
+    """A plan-cache hit launches with the Params its plan kept: nothing asks status_word() for
+    the word again, yet the call enqueued kernels that write it.  _launch itself records the
+    workspace's device, so the checked call still reads it (kvc_launch stubbed: no GPU)."""
+    class Ws:
+        def get_device(self):
+            return 6
+
+        def data_ptr(self):
+            return 4096
+
+    class Stream:
+        cuda_stream = 0
+
+    class Info:
+        workspace_bytes = 256
+
+    issued = []
+    monkeypatch.setattr(E.N, "launch", lambda p, t, w, n, s: issued.append(p.phases) or 0)
+    monkeypatch.setattr(E, "status_word", lambda device: pytest.fail("a word was asked for"))
+    params = E.N.Params(phases=E.N.PHASE_ALL)  # as a cached plan holds them
+
+    @E.status_checked
+    def cached_call():
+        E._launch(params, None, Ws(), Info(), Stream(), params.phases)
+
+    cached_call()
+    assert issued == [E.N.PHASE_ALL]
+    assert reads == [{6}]
+    E.set_status_check(False)
+    cached_call()  # check off: nothing recorded, nothing read
+    assert reads == [{6}] and getattr(E._check_state, "touched", None) is None
+
+
 def test_output_devices_of_a_result():
     """The native replay bypasses status_word(): the memo wrapper reads the devices of the
     result's CUDA tensors (none for CPU tensors or a non-list result)."""
