@@ -6,7 +6,7 @@ cascade_sum (SumKernel.cpp) adds each output column's rows either as a four-leve
 the inner-loop calls TensorIterator makes: one call over all columns, or -- when parallel_reduce
 splits the column dimension over threads (parallel_dim_reduction / find_split_dim) -- one call
 per thread chunk of ceil(cols / threads) columns with bounds rounded down to 128 bytes.  The HIP
-kernels (csrc/kvc.hip, col_ilp) take that chunk size per layer and derive the rest; this module
+kernels (csrc/kvc_attn.h, col_ilp) take that chunk size per layer and derive the rest; this module
 computes it from the reference process's thread count (torch.get_num_threads()).
 """
 import torch

@@ -1,4 +1,4 @@
-/* div5_check.c -- test infrastructure: the kernel's correctly rounded x / 5 (csrc/kvc.hip
+/* div5_check.c -- test infrastructure: the kernel's correctly rounded x / 5 (csrc/kvc_snapkv_keys.h
  * div5_rn: q0 = x * RN(1/5), exact FMA residual, one FMA correction; q0 when the residual is 0
  * or q0 is infinite) against IEEE x / 5.0f, bit for bit (NaN payloads aside).
  *   div5_check [STRIDE]   checks every STRIDE-th of the 2^32 fp32 patterns (default 1: all) */

@@ -10,7 +10,7 @@
 
 #include "kvc_serial.h"
 
-// Lane-by-lane model of wave_tiny_chain's level (csrc/kvc.hip): the segment [lo, hi) of at
+// Lane-by-lane model of wave_tiny_chain's level (csrc/kvc_select_chain.h): the segment [lo, hi) of at
 // most 64 positions in "lanes" (lane i = position lo + i); the median move, the ge / le ballots,
 // the g / s ranks from mbcnt counts, the rank -> lane tables of the forward permutes and the
 // partner fetch of the backward permutes, exactly as the kernel computes them.  Returns cut.
@@ -172,7 +172,7 @@ extern "C" float model_f16_to_f32(uint32_t h) { return kvc::f16_to_f32(h); }
 extern "C" uint32_t model_canon_nan_f16(uint32_t w) { return kvc::canon_nan_f16x2(w); }
 
 
-// ---- the select kernel's register heap (RegHeap in csrc/kvc.hip), 64 lanes simulated ---------
+// ---- the select kernel's register heap (RegHeap in csrc/kvc_select_chain.h), 64 lanes simulated
 // adjust() as the kernel computes it: per lane its chosen child from its children's keys, the
 // path from `top` by a chase of chosen children, the stop depth m as a count over path nodes,
 // then path depths < m take their chosen child's entry and depth m the value.  Checked slot by

@@ -26,7 +26,8 @@ SENTINEL = {"bf16": 0x7FA5, "fp16": 0x7DA5, "fp32": 0x7FA5A5A5}
 BITS = {"bf16": np.uint16, "fp16": np.uint16, "fp32": np.uint32}
 
 # the selection kernel kvc_launch dispatches for a call whose longest selecting zone is n
-# (csrc/kvc.hip launch_select: kSmallZone 8 192, kZoneMax 16 384, kZoneMaxGlobal 65 536)
+# (csrc/kvc.hip launch_select; csrc/kvc_device_util.h kSmallZone 8 192, kZoneMax 16 384,
+# kZoneMaxGlobal 65 536)
 KERNEL_EDGES = ((8192, "512-thread LDS"), (16384, "1024-thread LDS"),
                 (65536, "global scratch, u16 positions"), (1 << 24, "global scratch, u32 positions"))
 

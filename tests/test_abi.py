@@ -220,7 +220,7 @@ def test_plan_long_zone_gets_global_scratch():
     row += -row % 256
     idx_end = i1.index_offset + 32 * i1.index_row_stride * 4
     idx_end += -idx_end % 256
-    tiles = 32 * (n_cap // 64) * 4  # SCORE's per-tile statistics (level-0 counts), round 6
+    tiles = 32 * (n_cap // 64) * 4  # SCORE's per-tile region (unused by plain-norm rows), round 6
     assert i1.workspace_bytes == idx_end + 32 * row + tiles
 
 
@@ -235,7 +235,7 @@ def test_plan_zone_beyond_u16_positions_gets_u32_scratch():
     row += -row % 256
     idx_end = info.index_offset + 32 * info.index_row_stride * 4
     idx_end += -idx_end % 256
-    tiles = 32 * (n_cap // 64) * 4  # SCORE's per-tile statistics (level-0 counts), round 6
+    tiles = 32 * (n_cap // 64) * 4  # SCORE's per-tile region (unused by plain-norm rows), round 6
     assert info.workspace_bytes == idx_end + 32 * row + tiles
 
 
@@ -394,8 +394,8 @@ def test_header_states_the_phase_and_bounds_contracts():
 
 def test_scored_calls_reserve_the_tile_statistics_region():
     """kvc_plan reserves rows x norm_row_stride / 64 u32 after the index region for SCORE's
-    per-tile statistics (round 6): a snapkv row's tile norm maxima, a plain-norm row's level-0
-    ge / le counts -- the same size either way, and nothing for a call that selects nothing."""
+    per-tile region (round 6): a snapkv row's tile norm maxima, unused by a plain-norm row -- the
+    same size either way, and nothing for a call that selects nothing."""
     H, D = 4, 64
 
     def plan(mode):

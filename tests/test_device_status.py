@@ -1,7 +1,7 @@
 """The device status channel as a contract (include/kvc.h, kvc_device_status).
 
 KVC_DEV_SELECT_BOUNDS is raised by the selection kernels when a row's zone is longer than the
-kernel's capacity (csrc/kvc.hip select_body): the row then selects nothing and -- in the fused
+kernel's capacity (csrc/kvc_select.h select_body): the row then selects nothing and -- in the fused
 SELECT_GATHER kernel -- writes no output row.  kvc_launch always dispatches a sufficient capacity,
 so the guard is driven through kvc_debug_select_capacity, which launches the same kernels with a
 caller-chosen capacity.  (tests/conftest.py also asserts after every GPU test that the engine's

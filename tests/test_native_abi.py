@@ -53,7 +53,7 @@ def test_c_caller_fix_size_l2_matches_oracle(tmp_path, desc, algo, monkeypatch):
 
 
 def test_div5_matches_ieee_division():
-    """The snapkv pooling's x / 5 (csrc/kvc.hip div5_rn) equals IEEE x / 5.0f: every 61st of the
+    """The snapkv pooling's x / 5 (csrc/kvc_snapkv_keys.h div5_rn) equals IEEE x / 5.0f: every 61st of the
     2^32 fp32 patterns here (all of them: `div5_check 1`, ~1 min)."""
     src = os.path.join(ROOT, "tests", "native", "div5_check.c")
     exe = os.path.join(ROOT, "tests", "native", "_build", "div5_check")

@@ -186,7 +186,7 @@ def test_register_heap_matches_serial_heap_select(model):
 
 
 def test_tiny_chain_lane_model_matches_libstdcxx(model):
-    """wave_tiny_chain (csrc/kvc.hip: the chain's levels on segments of <= 64 positions from
+    """wave_tiny_chain (csrc/kvc_select_chain.h: the chain's levels on segments of <= 64 positions from
     registers -- ballots, mbcnt ranks, forward-permute rank tables, backward-permute swaps) as a
     lane-by-lane model (select_model.cpp tiny_level) gives libstdc++'s first-k set: heavy ties,
     sort and nth_element, the k boundaries, small rows that enter the tiny levels at once, and the

@@ -8,7 +8,7 @@ K / V thirds of one fused projection buffer), so their stride triples differ, an
 around a view is poison (tests/strided_layouts.py).  tests/test_strided_layouts.py proves on the
 CPU that a kernel ignoring the strides could not produce the expected bytes for these inputs.
 
-Which kernel path each block reaches (thresholds in csrc/kvc.hip: kSmallZone 8192, kZoneMax 16384,
+Which kernel path each block reaches (thresholds in csrc/kvc_device_util.h: kSmallZone 8192, kZoneMax 16384,
 kZoneMaxGlobal 65536, kSplitCopyRows 255):
   (a) score_tile at its three staging widths and gather_row / gather_block at every row width;
   (b) every layout, the copy-only launches, views and untouched layers;

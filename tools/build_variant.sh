@@ -10,7 +10,7 @@ extra=("$@")
 src="$R/cs3602-llm-inference-acceleration_amd/csrc/kvc.hip"
 inc="$R/include"
 if [ ${#extra[@]} -eq 0 ]; then
-  line=$(grep -E "^$name[[:space:]]" "$R/tools/ab_variants.txt" || true)
+  line=$(grep -E "^$name([[:space:]]|$)" "$R/tools/ab_variants.txt" || true)
   [ -n "$line" ] || { echo "variant $name not in tools/ab_variants.txt" >&2; exit 2; }
   read -r -a f <<< "$line"
   extra=("${f[@]:1}")
@@ -24,6 +24,7 @@ if [[ "${extra[0]}" == rev=* ]]; then
   src="$tmp/cs3602-llm-inference-acceleration_amd/csrc/kvc.hip"
   inc="$tmp/include"
 fi
+mkdir -p "$R/cs3602-llm-inference-acceleration_amd/kvcompress/_lib"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off \
     -fhip-fp32-correctly-rounded-divide-sqrt -I "$inc" "${extra[@]}" "$src" \
     -o "$R/cs3602-llm-inference-acceleration_amd/kvcompress/_lib/libkvc_$name.so" 2>&1 \
