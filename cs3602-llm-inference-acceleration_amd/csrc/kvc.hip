@@ -38,6 +38,7 @@
 #include "kvc_select.h"         // select_body, select_kernel, select_global / select_long
 #include "kvc_gather.h"         // gather_kernel, select_gather_kernel
 #include "kvc_attn.h"           // attn_accumulate / head-sum kernels
+#include "kvc_gather_dest.h"    // gather_dest_kernel (kvc_launch_dest)
 
 namespace kvc {
 
@@ -174,6 +175,67 @@ static inline size_t tmax_offset(const kvc_plan_info_t& info, int dtype) {
   return off;
 }
 
+// kvc_plan_dest / kvc_launch_dest: plan_impl, then the destinations of every layer with output
+// (include/kvc.h, "Caller-provided destinations").  dests == nullptr: plan_impl alone.
+static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_dest_t* dests,
+                          int nl, kvc_plan_info_t* info, bool fill) {
+  int rc = plan_impl(p, layers, nl, info, fill);
+  if (rc != KVC_OK || !dests) return rc;
+  if (p->flags & (KVC_FLAG_GATHER_FIXED | KVC_FLAG_GATHER_SELECTED)) return KVC_E_ARG;
+  const int es = esize(p->dtype);
+  const int64_t rowb = (int64_t)p->head_dim * es;
+  const int64_t B = p->batch, H = p->heads;
+  // byte span [lo, hi) of a [B, H, n, D] view
+  const auto span = [&](const void* base, const int64_t* st, int64_t n, uintptr_t* lo,
+                        uintptr_t* hi) {
+    const int64_t size[3] = {B, H, n};
+    int64_t neg = 0, pos = 0;
+    for (int d = 0; d < 3; ++d) {
+      const int64_t ext = (size[d] - 1) * st[d] * es;
+      (ext < 0 ? neg : pos) += ext;
+    }
+    *lo = (uintptr_t)base + neg;
+    *hi = (uintptr_t)base + pos + rowb;
+  };
+  for (int l = 0; l < nl; ++l) {
+    const kvc_layer_t& y = layers[l];
+    const kvc_dest_t& d = dests[l];
+    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
+    if (n_out == 0) continue;
+    if (d.reserved != 0 || (d.in_place != 0 && d.in_place != 1)) return KVC_E_ARG;
+    const int64_t* ks = d.k_stride;
+    const int64_t* vs = d.v_stride;
+    if ((B > 1 && ((ks[0] * es) % 16 || (vs[0] * es) % 16)) ||
+        (H > 1 && ((ks[1] * es) % 16 || (vs[1] * es) % 16)) ||
+        (n_out > 1 && ((ks[2] * es) % 16 || (vs[2] * es) % 16)))
+      return KVC_E_ALIGN;
+    if (d.in_place) {
+      if (y.k_out != y.k || y.v_out != y.v || memcmp(ks, y.k_stride, sizeof(y.k_stride)) ||
+          memcmp(vs, y.v_stride, sizeof(y.v_stride)))
+        return KVC_E_ARG;
+      // the row map must be strictly increasing with src(t) >= t
+      if ((y.n_select > 0 && y.sink_len > y.zone_start) ||
+          (y.tail_len > 0 && ((int64_t)y.zone_start + y.zone_len > y.tail_start ||
+                              y.sink_len > y.tail_start)))
+        return KVC_E_ARG;
+      // a zero stride (an expanded batch) would be written twice
+      if ((B > 1 && (ks[0] == 0 || vs[0] == 0)) || (H > 1 && (ks[1] == 0 || vs[1] == 0)) ||
+          (y.seq_len > 1 && (ks[2] == 0 || vs[2] == 0)))
+        return KVC_E_ARG;
+    } else {
+      uintptr_t slo[2], shi[2], dlo[2], dhi[2];
+      span(y.k, y.k_stride, y.seq_len, &slo[0], &shi[0]);
+      span(y.v, y.v_stride, y.seq_len, &slo[1], &shi[1]);
+      span(y.k_out, ks, n_out, &dlo[0], &dhi[0]);
+      span(y.v_out, vs, n_out, &dlo[1], &dhi[1]);
+      for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b)
+          if (dlo[a] < shi[b] && slo[b] < dhi[a]) return KVC_E_ARG;
+    }
+  }
+  return KVC_OK;
+}
+
 // Every launch goes through hipLaunchKernel, whose return value is this launch's own status (a
 // caller's pending HIP error is neither consumed nor reported as ours).
 template <typename... P, typename... A>
@@ -241,6 +303,24 @@ static int launch_gather(const LayerChunk& T, int nl, int H, int BH, const int32
                   dim3(kGatherThreads), 0, s, T, H, BH, idx, istride, shared, status, part, 0, nby);
 }
 
+// GATHER of a dest launch: grid = (rows, passes of the longest output that is not in place); an
+// in-place row is one workgroup's
+template <int DT, int NC>
+static int launch_gather_dest(const LayerChunk& T, const kvc_dest_t* dests, int nl, int H, int BH,
+                              const int32_t* idx, int64_t istride, int shared, uint32_t* status,
+                              hipStream_t s) {
+  DestChunk D;
+  memset(&D, 0, sizeof(D));
+  memcpy(D.d, dests, (size_t)nl * sizeof(kvc_dest_t));
+  int64_t work = 0;  // longest output copied by token blocks
+  for (int l = 0; l < nl; ++l)
+    if (!dests[l].in_place && T.l[l].n_out > work) work = T.l[l].n_out;
+  constexpr int rows_per = dest_pass_rows(NC);
+  const int nby = work > 0 ? (int)((work + rows_per - 1) / rows_per) : 1;
+  return launch_k(gather_dest_kernel<DT, NC>, dim3((unsigned)(nl * BH), (unsigned)nby),
+                  dim3(kGatherThreads), 0, s, T, D, H, BH, idx, istride, shared, status);
+}
+
 // SELECT over the rows of a chunk (BH rows per layer, workspace row ly->row0 + blockIdx % BH):
 // the LDS kernels (512-thread rows for zones up to kSmallZone, else 1 024-thread rows) or, for
 // zones longer than kZoneMax, the global-scratch kernels (u32 positions beyond kZoneMaxGlobal).
@@ -286,9 +366,12 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
 // One chunk of <= kArgLayers layers: SCORE, then SELECT_GATHER (or SELECT and GATHER as two
 // kernels with KVC_FLAG_SPLIT_SELECT_GATHER, or GATHER alone for copy-only / external-index
 // calls), each kernel with the chunk's table by value.
+// dests != nullptr (kvc_launch_dest): SELECT and GATHER always as two kernels, the GATHER into the
+// layers' destinations (gather_dest_kernel).
 template <int DT, int NC>
 static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, const kvc_layer_t* layers,
-                        int nl, int c0, int cn, char* w, hipStream_t s) {
+                        int nl, int c0, int cn, char* w, hipStream_t s,
+                        const kvc_dest_t* dests = nullptr) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
   const int H = p->heads, BH = p->batch * p->heads;
@@ -329,7 +412,7 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
   const int n_cap = (int)nstride;  // longest zone of the call, rounded to 64
   if ((p->phases & KVC_PHASE_SELECT) && sel && !ext) {
     const bool fuse_sg = (p->phases & KVC_PHASE_GATHER) && max_out > 0 && !stamps &&
-                         !long_zone && part == PART_ALL &&
+                         !long_zone && part == PART_ALL && !dests &&
                          !(p->flags & KVC_FLAG_SPLIT_SELECT_GATHER);
     if (fuse_sg) {  // this chunk's gather happens inside the select kernel
       const int rows = cn * BH;
@@ -376,6 +459,9 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                            long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && dests)
+    return launch_gather_dest<DT, NC>(T, dests + c0, cn, H, BH, idx, istride,
+                                      (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
   if ((p->phases & KVC_PHASE_GATHER) && max_part > 0)
     rc = launch_gather<DT, NC>(T, cn, H, BH, idx, istride,
                                (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, max_part, part,
@@ -595,11 +681,21 @@ int kvc_plan(const kvc_params_t* params, kvc_layer_t* layers, int num_layers,
   return kvc::plan_impl(params, layers, num_layers, info, true);
 }
 
+int kvc_plan_dest(const kvc_params_t* params, kvc_layer_t* layers, const kvc_dest_t* dests,
+                  int num_layers, kvc_plan_info_t* info) {
+  return kvc::plan_dest_impl(params, layers, dests, num_layers, info, true);
+}
+
 int kvc_launch(const kvc_params_t* p, const kvc_layer_t* layers, int nl, void* ws,
                size_t ws_bytes, kvc_stream_t stream) {
+  return kvc_launch_dest(p, layers, nullptr, nl, ws, ws_bytes, stream);
+}
+
+int kvc_launch_dest(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_dest_t* dests,
+                    int nl, void* ws, size_t ws_bytes, kvc_stream_t stream) {
   using namespace kvc;
   kvc_plan_info_t info;
-  int rc = plan_impl(p, const_cast<kvc_layer_t*>(layers), nl, &info, false);
+  int rc = plan_dest_impl(p, const_cast<kvc_layer_t*>(layers), dests, nl, &info, false);
   if (rc != KVC_OK) return rc;
   if (nl == 0) return KVC_OK;
   if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
@@ -611,7 +707,7 @@ int kvc_launch(const kvc_params_t* p, const kvc_layer_t* layers, int nl, void* w
     rc = with_dtype(p->dtype, [&](auto dt) {
       return with_nc(nc, [&](auto ncv) {
         return launch_chunk<decltype(dt)::value, decltype(ncv)::value>(p, info, layers, nl, c0,
-                                                                       cn, w, s);
+                                                                       cn, w, s, dests);
       });
     });
   }

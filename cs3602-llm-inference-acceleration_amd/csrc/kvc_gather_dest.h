@@ -1,0 +1,139 @@
+// kvc_gather_dest.h -- GATHER into caller-provided destinations (kvc_launch_dest): strided
+// k_out / v_out views, or the layer's own K / V compacted in place.
+#pragma once
+
+#include "kvc_gather.h"
+
+namespace kvc {
+
+// The destinations of a chunk's layers travel by value beside its LayerChunk (3.5 KiB).
+struct DestChunk {
+  kvc_dest_t d[kArgLayers];
+};
+
+constexpr int kDestIters = 4;  // 16-B units of K and of V per thread and pass
+// output rows of one pass (one workgroup): 64 rows of 256 B, 32 of 512 B, 102 of 160 B
+__host__ __device__ constexpr int dest_pass_rows(int nc) {
+  return kGatherThreads * kDestIters / nc;
+}
+
+// Copies the rows gather_kernel would copy from the same index region (PART_ALL), to
+// b * os0 + h * os1 + t * os2 of the layer's kvc_dest_t instead of a contiguous output.
+//
+// grid = (rows, nby).  A layer that is NOT in place has no ordering constraint: block (row, by)
+// copies the one pass of dest_pass_rows(NC) output rows from by * dest_pass_rows(NC) on, like
+// gather_block.
+//
+// An IN-PLACE layer (destination == source) is copied by ONE workgroup per (layer, b, h) row --
+// block (row, 0); the others return -- in passes of consecutive output rows, ascending.  Why one
+// barrier per pass makes that a correct memmove:
+//   * the row map is strictly increasing with src(t) >= t (kvc_plan_dest refuses anything else;
+//     ascending indices are the index region's contract), so output row t only ever overwrites
+//     a row that is the source of output rows <= t;
+//   * within pass p every wave loads its units of K and V into registers, waits until those
+//     loads have RETURNED (s_waitcnt vmcnt(0): a bare s_barrier does not wait for outstanding
+//     global loads), meets the other waves at the barrier, and only then stores.  So no store of
+//     pass p can land before a load of pass p -- of any wave -- has its data;
+//   * the sources of pass p+1 lie strictly above every destination of passes <= p (src(t) >= t),
+//     so its loads need no ordering against earlier stores; its stores follow its own barrier,
+//     which every wave reaches only after its own loads of pass p (and p+1) have returned, so
+//     they cannot overtake a load of an earlier pass either.
+// Sink rows have src == dst and are not touched.  Rows [n_out, S) are never written.
+template <int DT, int NC>
+__global__ void __launch_bounds__(kGatherThreads)
+    gather_dest_kernel(const LayerChunk T, const DestChunk Dd, int H, int BH,
+                       const int32_t* __restrict__ gidx, int64_t idx_stride, int shared,
+                       uint32_t* status) {
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  constexpr int ROWS = dest_pass_rows(NC);
+  const int li = (int)blockIdx.x / BH;
+  const kvc_layer_t* ly = T.l + li;
+  const kvc_dest_t* de = Dd.d + li;
+  const int r = (int)blockIdx.x - li * BH;
+  const int n_out = ly->n_out;
+  const bool inplace = de->in_place != 0;
+  const int sink = ly->sink_len, nsel = ly->n_select;
+  int t_begin, t_end;
+  if (inplace) {
+    if (blockIdx.y != 0) return;
+    t_begin = sink;
+    t_end = n_out;
+  } else {
+    t_begin = (int)blockIdx.y * ROWS;
+    t_end = min(n_out, t_begin + ROWS);
+  }
+  if (t_begin >= t_end) return;
+  const int b = r / H, h = r - (r / H) * H;
+  const char* kb = static_cast<const char*>(ly->k) +
+                   ((int64_t)b * ly->k_stride[0] + (int64_t)h * ly->k_stride[1]) * ESZ;
+  const char* vb = static_cast<const char*>(ly->v) +
+                   ((int64_t)b * ly->v_stride[0] + (int64_t)h * ly->v_stride[1]) * ESZ;
+  const int64_t kss = ly->k_stride[2] * ESZ, vss = ly->v_stride[2] * ESZ;
+  char* ko = static_cast<char*>(ly->k_out) +
+             ((int64_t)b * de->k_stride[0] + (int64_t)h * de->k_stride[1]) * ESZ;
+  char* vo = static_cast<char*>(ly->v_out) +
+             ((int64_t)b * de->v_stride[0] + (int64_t)h * de->v_stride[1]) * ESZ;
+  const int64_t kos = de->k_stride[2] * ESZ, vos = de->v_stride[2] * ESZ;
+  // index row of (layer, b, h); KVC_FLAG_SHARED_INDEX: (layer, b)'s row serves every head
+  const int32_t* irow = gidx + (int64_t)((ly->row0 + r) / (shared ? H : 1)) * idx_stride;
+  const int zone_len = ly->zone_len, zone_start = ly->zone_start, tail_start = ly->tail_start;
+  for (int t0 = t_begin; t0 < t_end; t0 += ROWS) {  // ascending passes
+    const int nu = min(ROWS, t_end - t0) * NC;
+    uint4 xk[kDestIters], xv[kDestIters];
+    bool gat[kDestIters];
+    int zi[kDestIters];
+    // the index loads of all units are issued first.  (The compiler still waits for each unit's
+    // index right before that unit's K / V loads -- one s_waitcnt vmcnt(0) per unit in the gfx950
+    // ISA -- so the four units' K / V loads do not go out back to back: a known cost, not tuned.)
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      const int t = t0 + u / NC;
+      gat[i] = u < nu && t >= sink && t < sink + nsel;
+      zi[i] = gat[i] ? irow[t - sink] : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      if (u < nu) {
+        const int t = t0 + u / NC, c = u - (u / NC) * NC;
+        int src;
+        if (t < sink) {
+          src = t;
+        } else if (gat[i]) {
+          if ((zi[i] < 0 || zi[i] >= zone_len) && status)  // never read outside the zone: clamp
+            atomicOr(status, (uint32_t)KVC_DEV_INDEX_RANGE);
+          src = zone_start + min(max(zi[i], 0), zone_len - 1);
+        } else {
+          src = tail_start + (t - sink - nsel);
+        }
+        xk[i] = *reinterpret_cast<const uint4*>(kb + src * kss + c * 16);
+        xv[i] = *reinterpret_cast<const uint4*>(vb + src * vss + c * 16);
+      }
+    }
+    if (inplace) {  // uniform over the workgroup
+      // every load of this pass has returned in this wave, then in all waves, before any store
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      if (u < nu) {
+        const int t = t0 + u / NC, c = u - (u / NC) * NC;
+        uint4 a = xk[i], q = xv[i];
+        if (gat[i]) {  // torch.gather's NaN rewrite (gathered segment only)
+          a = canon_nan_dt<DT>(a);
+          q = canon_nan_dt<DT>(q);
+        }
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        __builtin_nontemporal_store(u32x4{a.x, a.y, a.z, a.w},
+                                    reinterpret_cast<u32x4*>(ko + t * kos + c * 16));
+        __builtin_nontemporal_store(u32x4{q.x, q.y, q.z, q.w},
+                                    reinterpret_cast<u32x4*>(vo + t * vos + c * 16));
+      }
+    }
+  }
+}
+
+}  // namespace kvc

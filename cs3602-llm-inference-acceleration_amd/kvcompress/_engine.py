@@ -36,6 +36,12 @@ class Segments:
     score_mode: int = N.KVC_SCORE_NORM
     pool_kernel: int = 0
     ext_index: Optional[torch.Tensor] = None  # [B, H, n_select] int64 zone-local, ascending
+    # caller-provided destination (kvc_launch_dest): [B, H, S_d >= n_out, D] views whose rows
+    # [0, n_out) receive the output; the layer's own keys / values = compacted in place
+    k_dest: Optional[torch.Tensor] = None
+    v_dest: Optional[torch.Tensor] = None
+    dest_checked: bool = False  # dest_call() has run _check_dest_tensors on this destination
+    dest_verified: bool = False  # ... and _check_dest: the launch does not repeat it
 
 
 _SUPPORTED = {torch.bfloat16: N.KVC_BF16, torch.float16: N.KVC_F16, torch.float32: N.KVC_F32}
@@ -229,6 +235,15 @@ def execute(jobs: List[Segments], out_list: list, order: int, algo: int):
                 raise ValueError(f"kvcompress: the stable tie policy selects from zones of at most "
                                  f"{STABLE_MAX_ZONE} positions (layer {j.layer_idx}: "
                                  f"{j.zone_len}); use the reference policy for longer zones")
+    if _defer(jobs, lambda: execute(jobs, out_list, order, algo), out_list):
+        return  # a call with `out`: dest_call() launches once every destination is checked
+    jobs, dest_jobs = _split_dest_jobs(jobs)
+    for j in dest_jobs:  # jobs that carry destinations of their own (no `out` call in progress)
+        _check_dest(j)
+    if dest_jobs:
+        _run_dest(dest_jobs, out_list, order, algo)
+        if not jobs:
+            return
     fast = _one_plain_group(jobs)
     if fast is not None:
         _run_plain(*fast, jobs, out_list, order, algo)
@@ -273,11 +288,15 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H):
+def _upload(params, table, device, js, B, H, dests=None):
     """Plan one table and allocate its workspace.  The table itself travels in the kernels'
     arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    rc, info = N.plan(params, table)
-    N.check(rc, "kvc_plan")
+    if dests is None:
+        rc, info = N.plan(params, table)
+        N.check(rc, "kvc_plan")
+    else:
+        rc, info = N.plan_dest(params, table, dests)
+        N.check(rc, "kvc_plan_dest")
     ws = torch.empty(max(int(info.workspace_bytes), 256), dtype=torch.uint8, device=device)
     if params.external_index:
         istride = int(info.index_row_stride)
@@ -290,7 +309,7 @@ def _upload(params, table, device, js, B, H):
     return ws, info
 
 
-def _launch(params, table, ws, info, stream, phases):
+def _launch(params, table, ws, info, stream, phases, dests=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
@@ -301,11 +320,15 @@ def _launch(params, table, ws, info, stream, phases):
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        rc = N.launch(params, table, ws.data_ptr(), int(info.workspace_bytes),
-                      stream.cuda_stream)
+        if dests is None:
+            rc = N.launch(params, table, ws.data_ptr(), int(info.workspace_bytes),
+                          stream.cuda_stream)
+        else:
+            rc = N.launch_dest(params, table, dests, ws.data_ptr(), int(info.workspace_bytes),
+                               stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch")
+        N.check(rc, "kvc_launch" if dests is None else "kvc_launch_dest")
         if _timer is not None:
             _timer.records.append((name, a, b))
     params.phases = saved
@@ -600,13 +623,20 @@ def _plan_plain(dtype, B, H, D, order, algo, segs):
     return table, info, ws, p, n_outs
 
 
-def _build_table(device, dtype, B, H, D, js):
+def _build_table(device, dtype, B, H, D, js, dest=False):
     """Layer table of a group (pointers, strides, segment bounds) and its output tensors; `keep`
-    holds prepared (contiguous) input copies alive until the launch has been issued."""
+    holds prepared (contiguous) input copies alive until the launch has been issued.  dest=True
+    (every job carries a destination): the outputs are rows [0, n_out) of the jobs' k_dest /
+    v_dest, whose strides _dest_table() puts into the kvc_dest_t array."""
     es = _ESIZE[dtype]
     rows_ok = (D * es) % 16 == 0
     n_outs = [j.sink_len + j.n_select + j.tail_len for j in js]
-    kos, vos, kops, vops = _outputs(device, dtype, B, H, D, n_outs)
+    if dest:
+        kos = [j.k_dest.narrow(2, 0, n) for j, n in zip(js, n_outs)]
+        vos = [j.v_dest.narrow(2, 0, n) for j, n in zip(js, n_outs)]
+        kops, vops = [t.data_ptr() for t in kos], [t.data_ptr() for t in vos]
+    else:
+        kos, vos, kops, vops = _outputs(device, dtype, B, H, D, n_outs)
     # one pass per layer: pointers, strides, segment bounds (inputs that are not plain
     # contiguous 16-B aligned rows go through _prep; prepared copies stay alive in `keep`)
     rows, keep = [], []
@@ -649,22 +679,29 @@ def execute_shared(jobs: List[Segments], out_list: list, fill, overlap=False):
     copy kernel is enqueued on the same stream.  overlap=True: the sink and tail rows (which no
     index decides) are copied on a side stream forked before `fill` and joined after the selected
     rows' copy (KVC_FLAG_GATHER_FIXED / _SELECTED), so they move while `fill` selects."""
+    if _defer(jobs, lambda: execute_shared(jobs, out_list, fill, overlap), out_list):
+        return  # a call with `out`: dest_call() launches once every destination is checked
     if _recording is not None:
         _recording.append(None)
-    groups = {}
     for j in jobs:
+        if j.k_dest is not None:
+            _check_dest(j)
+    groups = {}
+    for j in jobs:  # jobs with a destination form groups of their own (no side-stream copy)
         B, H, _, D = _check_tensors(j)
-        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D), []).append(j)
-    for (device, dtype, B, H, D), js in groups.items():
+        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D, j.k_dest is not None),
+                          []).append(j)
+    for (device, dtype, B, H, D, dest), js in groups.items():
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
-            table, kos, vos, keep = _build_table(device, dtype, B, H, D, js)
+            table, kos, vos, keep = _build_table(device, dtype, B, H, D, js, dest)
+            dests = _dest_table(js, table) if dest else None
             p = _params(dtype, B, H, D, N.KVC_ASC, N.KVC_ALGO_SORT, True, shared=True)
-            rc, info = N.plan(p, table)
-            N.check(rc, "kvc_plan")
+            rc, info = N.plan_dest(p, table, dests) if dest else N.plan(p, table)
+            N.check(rc, "kvc_plan_dest" if dest else "kvc_plan")
             ws = torch.empty(max(int(info.workspace_bytes), 256), dtype=torch.uint8,
                              device=torch.device("cuda", device))
-            side = side_stream(device) if overlap and _timer is None else None
+            side = side_stream(device) if overlap and _timer is None and not dest else None
             if side is not None:
                 pf = _params(dtype, B, H, D, N.KVC_ASC, N.KVC_ALGO_SORT, True, shared=True)
                 pf.flags |= N.FLAG_GATHER_FIXED
@@ -676,11 +713,202 @@ def execute_shared(jobs: List[Segments], out_list: list, fill, overlap=False):
                     _launch(pf, table, ws, info, side[0], pf.phases)
                 fill(js, ws.data_ptr() + int(info.index_offset), int(info.index_row_stride),
                      stream)
-                _launch(p, table, ws, info, stream, p.phases)
+                _launch(p, table, ws, info, stream, p.phases, dests)
             finally:
                 if side is not None:  # `stream` continues only after the side copy, on every
                     side[2].record(side[0])  # exit path (outputs and workspace are freed on it)
                     side[2].wait(stream)
+            del keep
+        for j, ko, vo in zip(js, kos, vos):
+            out_list[j.layer_idx] = (ko, vo)
+
+
+# ---------------------------------------------------------------------------------------------
+# Caller-provided destinations (kvc_plan_dest / kvc_launch_dest; INTEGRATION.md, "Destinations")
+# ---------------------------------------------------------------------------------------------
+_dest_state = _threading.local()  # .ctx: the _DestCall of the compress call in progress
+
+
+class _DestCall:
+    """Destinations of one compress call (the `out` kwarg): per layer "inplace", a (K_dst, V_dst)
+    pair or None.  While the method runs, execute() / execute_shared() launch nothing: they give
+    every job its layer's destination and park the launch in `pending` [(jobs, run, out_list)];
+    `done` collects the layers whose engine job took its destination.  `rollback` holds what undoes
+    the method's side effects (h2o_attention's manager update) when a check then fails."""
+    __slots__ = ("dests", "done", "pending", "rollback")
+
+    def __init__(self, dests):
+        self.dests, self.done, self.pending, self.rollback = dests, set(), [], []
+
+
+def dest_call_active():
+    """True inside a compress call that carries destinations (such calls bypass the call memo,
+    the plan cache and h2o_attention's step replay)."""
+    return getattr(_dest_state, "ctx", None) is not None
+
+
+def on_dest_error(undo):
+    """Inside a call with `out`: register undo() to run if the call raises before it launches."""
+    ctx = getattr(_dest_state, "ctx", None)
+    if ctx is not None:
+        ctx.rollback.append(undo)
+
+
+def _defer(jobs, run, out_list):
+    """Inside a call with `out` (dest_call): give the jobs their layers' destinations, park the
+    launch and return True; otherwise False."""
+    ctx = getattr(_dest_state, "ctx", None)
+    if ctx is None:
+        return False
+    for j in jobs:
+        d = ctx.dests[j.layer_idx] if j.k_dest is None else None
+        if d is not None:
+            j.k_dest, j.v_dest = (j.keys, j.values) if d == "inplace" else d
+            j.dest_checked = True
+            ctx.done.add(j.layer_idx)
+    ctx.pending.append((jobs, run, out_list))
+    return True
+
+
+def _split_dest_jobs(jobs):
+    """(jobs without, jobs with a destination)."""
+    plain = [j for j in jobs if j.k_dest is None]
+    if len(plain) == len(jobs):
+        return jobs, []
+    return plain, [j for j in jobs if j.k_dest is not None]
+
+
+def _takes_as_is(t):
+    """_prep's conditions without the copy: last dim contiguous, 16-B aligned pointer and strides."""
+    es = t.element_size()
+    return ((t.stride(3) == 1 or t.size(3) == 1) and t.data_ptr() % 16 == 0 and
+            (t.size(3) * es) % 16 == 0 and
+            all((t.stride(d) * es) % 16 == 0 or t.size(d) == 1 for d in range(3)))
+
+
+def _is_inplace(src, dst):
+    return dst is src or (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()
+                          and dst.shape == src.shape)
+
+
+def _check_dest_tensors(li, k, v, kd, vd):
+    """Everything about layer `li`'s destination that does not depend on the output length.
+    Raises ValueError / TypeError naming the layer; nothing is copied or enqueued."""
+    for name, src, dst in (("K", k, kd), ("V", v, vd)):
+        what = f"layer {li}: {name} destination"
+        if not isinstance(dst, torch.Tensor):
+            raise TypeError(f"{what} must be a tensor, got {type(dst).__name__}")
+        if _is_inplace(src, dst):
+            if not _takes_as_is(src):
+                raise ValueError(
+                    f"layer {li}: {name} cannot be compacted in place: the engine would have to "
+                    "copy it first (last dim not contiguous, or a pointer / stride that is not "
+                    "a multiple of 16 bytes)")
+            if any(src.stride(d) == 0 and src.size(d) > 1 for d in range(3)):
+                raise ValueError(f"layer {li}: {name} cannot be compacted in place: stride 0 on "
+                                 "a dim larger than 1 (an expanded tensor would be written twice)")
+            continue
+        if dst.dtype != src.dtype:
+            raise TypeError(f"{what} has dtype {dst.dtype}, the layer {src.dtype}")
+        if dst.dim() != 4 or src.dim() != 4 or (dst.shape[0], dst.shape[1], dst.shape[3]) != \
+                (src.shape[0], src.shape[1], src.shape[3]):
+            raise ValueError(f"{what} must be [B, H, S_d, D] with the layer's B, H, D "
+                             f"{tuple(src.shape)}; got {tuple(dst.shape)}")
+        if dst.stride(3) != 1 and dst.size(3) > 1:
+            raise ValueError(f"{what}: the last dim must be contiguous (stride "
+                             f"{dst.stride(3)})")
+        es = dst.element_size()
+        if any((dst.stride(d) * es) % 16 and dst.size(d) > 1 for d in range(3)) or \
+                (dst.size(3) * es) % 16:
+            raise ValueError(f"{what}: strides {tuple(dst.stride())} are not multiples of 16 "
+                             "bytes (a destination is never copied)")
+        if dst.device != src.device:
+            raise ValueError(f"{what} is on {dst.device}, the layer on {src.device}")
+        if dst.data_ptr() % 16:
+            raise ValueError(f"{what}: pointer not 16-byte aligned (a destination is never "
+                             "copied)")
+    if _is_inplace(k, kd) != _is_inplace(v, vd):
+        raise ValueError(f"layer {li}: K and V must both be compacted in place or neither")
+
+
+def _span(t, n):
+    """Byte span [lo, hi) of rows [0, n) of a [B, H, S, D] view (kvc_plan_dest's span)."""
+    es = t.element_size()
+    ext = [(sz - 1) * st * es for sz, st in ((t.size(0), t.stride(0)), (t.size(1), t.stride(1)),
+                                             (n, t.stride(2)))]
+    lo = t.data_ptr() + sum(e for e in ext if e < 0)
+    return lo, t.data_ptr() + sum(e for e in ext if e > 0) + t.size(3) * es
+
+
+def _check_dest(j: Segments):
+    """The destination of one job: _check_dest_tensors, then what depends on its segments."""
+    if j.dest_verified:
+        return
+    li, k, v = j.layer_idx, j.keys, j.values
+    if not j.dest_checked:
+        _check_dest_tensors(li, k, v, j.k_dest, j.v_dest)
+    n = j.sink_len + j.n_select + j.tail_len
+    if n == 0:
+        return
+    if _is_inplace(k, j.k_dest):
+        if k.data_ptr() == v.data_ptr():
+            raise ValueError(f"layer {li}: K and V share their memory: not compacted in place")
+        ordered = ((j.n_select == 0 or j.sink_len <= j.zone_start) and
+                   (j.tail_len == 0 or (j.zone_start + j.zone_len <= j.tail_start and
+                                        j.sink_len <= j.tail_start)))
+        if not ordered:
+            raise ValueError(
+                f"layer {li}: cannot be compacted in place: its segments (sink {j.sink_len}, zone "
+                f"[{j.zone_start}, {j.zone_start + j.zone_len}), tail [{j.tail_start}, "
+                f"{j.tail_start + j.tail_len})) overlap or are out of order (e.g. "
+                "streaming_llm with recent_size=0, whose result is longer than its input)")
+        return
+    for name, dst in (("K", j.k_dest), ("V", j.v_dest)):
+        if dst.size(2) < n:
+            raise ValueError(f"layer {li}: {name} destination holds {dst.size(2)} rows, the "
+                             f"result has {n}")
+        lo, hi = _span(dst, n)
+        for sname, src in (("K", k), ("V", v)):
+            slo, shi = _span(src, src.size(2))
+            if lo < shi and slo < hi:
+                raise ValueError(f"layer {li}: {name} destination overlaps the layer's {sname} "
+                                 "(use out=\"inplace\" to compact a cache onto itself)")
+
+
+def _dest_table(js, table):
+    """kvc_dest_t array of a group whose layer table _build_table(dest=True) made."""
+    dests = np.zeros(len(js), dtype=N.DEST_DTYPE)
+    for i, j in enumerate(js):
+        inplace = _is_inplace(j.keys, j.k_dest)
+        # an in-place layer's strides are its (possibly size-1-dim-normalised) input strides
+        dests[i] = ((table["k_stride"][i] if inplace else j.k_dest.stride()[:3]),
+                    (table["v_stride"][i] if inplace else j.v_dest.stride()[:3]),
+                    1 if inplace else 0, 0)
+    return dests
+
+
+def _run_dest(jobs, out_list, order, algo):
+    """The jobs of a call that carry destinations (checked by the caller): one kvc_launch_dest
+    per (device, dtype, B, H, D) group.  No plan cache, and never recorded for the call memo."""
+    if _recording is not None:
+        _recording.append(None)
+    groups = {}
+    for j in jobs:
+        B, H, _, D = _check_tensors(j)
+        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D), []).append(j)
+    for (device, dtype, B, H, D), js in groups.items():
+        external = any(j.ext_index is not None for j in js)
+        if external and not all(j.ext_index is not None or j.n_select == 0 for j in js):
+            raise RuntimeError("mixed external / engine-selected layers in one group")
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            table, kos, vos, keep = _build_table(device, dtype, B, H, D, js, True)
+            dests = _dest_table(js, table)
+            p = _params(dtype, B, H, D, order, algo, external)
+            ws, info = _upload(p, table, device, js, B, H, dests)
+            _launch(p, table, ws, info, stream, p.phases, dests)
+            if _timer is not None and _timer.workspaces is not None:
+                _timer.workspaces.append((ws, info))
             del keep
         for j, ko, vo in zip(js, kos, vos):
             out_list[j.layer_idx] = (ko, vo)
@@ -738,6 +966,25 @@ class _Replay:
     __slots__ = ("actions", "table", "n_jobs", "n_outs", "params", "ws", "ws_bytes", "keep")
 
 
+def _slice_of(inp, res):
+    """(start, length) when the (K, V) pair `res` is the dim-2 slice [start, start + length) of
+    the input pair `inp` (same storage, same strides), else None."""
+    k, v = inp
+    rk, rv = res
+    st = k.stride(2)
+    if (rk.untyped_storage().data_ptr() != k.untyped_storage().data_ptr() or
+            rk.shape[:2] != k.shape[:2] or rk.shape[3] != k.shape[3] or
+            rk.stride() != k.stride() or st == 0 or
+            (rk.storage_offset() - k.storage_offset()) % st):
+        return None
+    start = (rk.storage_offset() - k.storage_offset()) // st
+    if not (rv.untyped_storage().data_ptr() == v.untyped_storage().data_ptr() and
+            rv.shape == rk.shape and rv.stride() == v.stride() and
+            rv.storage_offset() - v.storage_offset() == start * v.stride(2)):
+        return None
+    return start, rk.shape[2]
+
+
 def _record(kvl, out, launches):
     """A _Replay of one recorded call, or None when the call is not replayable (a general-path
     launch, more than one launch, or a layer that is neither passed through, a dim-2 slice of
@@ -761,20 +1008,10 @@ def _record(kvl, out, launches):
         if i in job_of:
             acts[i] = (2, job_of[i], 0)
             continue
-        k, v = inp
-        rk, rv = res
-        st = k.stride(2)
-        if (rk.untyped_storage().data_ptr() != k.untyped_storage().data_ptr() or
-                rk.shape[:2] != k.shape[:2] or rk.shape[3] != k.shape[3] or
-                rk.stride() != k.stride() or st == 0 or
-                (rk.storage_offset() - k.storage_offset()) % st):
+        sl = _slice_of(inp, res)
+        if sl is None:
             return None
-        start = (rk.storage_offset() - k.storage_offset()) // st
-        if not (rv.untyped_storage().data_ptr() == v.untyped_storage().data_ptr() and
-                rv.shape == rk.shape and rv.stride() == v.stride() and
-                rv.storage_offset() - v.storage_offset() == start * v.stride(2)):
-            return None
-        acts[i] = (1, start, rk.shape[2])
+        acts[i] = (1, sl[0], sl[1])
     rec.actions = acts
     return rec
 
@@ -794,6 +1031,10 @@ def memoized(fn):
 
     @functools.wraps(fn)
     def wrapper(past_key_values, *args, **kwargs):
+        out = kwargs.pop("out", None)  # extension kwarg: destinations (dest_call)
+        if out is not None:
+            return _checked_call(lambda: dest_call(fn, past_key_values, out, args, kwargs),
+                                 _output_devices)
         return _checked_call(lambda: _memo_call(past_key_values, *args, **kwargs),
                              _output_devices)
 
@@ -844,3 +1085,131 @@ def memoized(fn):
 def ctypes_addr(obj):
     import ctypes
     return ctypes.addressof(obj)
+
+
+# ---------------------------------------------------------------------------------------------
+# The `out` kwarg of every compress function ("Destinations")
+# ---------------------------------------------------------------------------------------------
+def with_out(fn):
+    """Give a compress entry point that is not `memoized` the `out` kwarg (dest_call)."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapper(past_key_values, *args, **kwargs):
+        out = kwargs.pop("out", None)
+        if out is None:
+            return fn(past_key_values, *args, **kwargs)
+        return _checked_call(lambda: dest_call(fn, past_key_values, out, args, kwargs),
+                             _output_devices)
+    return wrapper
+
+
+def dest_call(fn, past_key_values, out, args, kwargs):
+    """fn(past_key_values, *args, **kwargs) with its results written where `out` says.
+
+    out="inplace": every layer the call changes is compacted at the front of its own K / V
+    memory and comes back as (k.narrow(2, 0, n), v.narrow(2, 0, n)); untouched layers come back
+    as the same objects.  out=[(K_dst, V_dst) | None, ...], one entry per layer: a layer with an
+    entry ends up in K_dst[:, :, :n] / V_dst[:, :, :n] whatever the method does with it
+    (gathered, sliced or left alone -- the latter two are copied); None = the default behaviour,
+    "inplace" = that layer as under out="inplace".
+
+    The call runs `fn` itself (no call memo, no plan cache, no step replay) with the
+    destinations visible to execute() / execute_shared(), then moves the layers that came back
+    as the input or as a slice of it with copy-only engine jobs."""
+    from .utils import normalize_kv_cache
+    kvl = list(normalize_kv_cache(past_key_values))
+    L = len(kvl)
+    if isinstance(out, str):
+        if out != "inplace":
+            raise ValueError(f"out={out!r}: expected None, \"inplace\" or a list with one "
+                             "(K_dst, V_dst) pair or None per layer")
+        dests = ["inplace"] * L
+    elif isinstance(out, (list, tuple)):
+        if len(out) != L:
+            raise ValueError(f"out has {len(out)} entries for {L} layers")
+        dests = []
+        for i, d in enumerate(out):
+            if d is None or (isinstance(d, str) and d == "inplace"):
+                dests.append(d)
+                continue
+            if not (isinstance(d, (list, tuple)) and len(d) == 2):
+                raise TypeError(f"layer {i}: out entry must be a (K_dst, V_dst) pair, "
+                                "\"inplace\" or None")
+            dests.append(tuple(d))
+    else:
+        raise TypeError(f"out must be None, \"inplace\" or a list, got {type(out).__name__}")
+    seen = {}
+    for i, ((k, v), d) in enumerate(zip(kvl, dests)):  # before anything is enqueued
+        if d is None:
+            continue
+        kd, vd = (k, v) if d == "inplace" else d
+        _check_dest_tensors(i, k, v, kd, vd)
+        if d == "inplace" and k.numel() and v.numel():
+            for name, t in (("K", k), ("V", v)):
+                ptr = t.data_ptr()
+                if ptr in seen:
+                    raise ValueError(f"layer {i}: {name} shares its memory with {seen[ptr]}: "
+                                     "not compacted in place")
+                seen[ptr] = f"layer {i}'s {name}"
+    ctx = _DestCall(dests)
+    prev = getattr(_dest_state, "ctx", None)
+    try:
+        _dest_state.ctx = ctx
+        try:
+            res = fn(kvl, *args, **kwargs)  # launches nothing on K / V: see _defer()
+        finally:
+            _dest_state.ctx = prev
+        if not isinstance(res, list):
+            res = list(res)
+        moves = _dest_moves(kvl, res, dests, ctx)
+        # every job of the call -- the method's and the copies -- is checked before any launches
+        every = [j for jobs, _, _ in ctx.pending for j in jobs] + moves
+        for j in every:
+            if j.k_dest is not None:
+                _check_dest(j)
+                j.dest_verified = True
+        for j in every:
+            _check_tensors(j)
+    except BaseException:
+        for undo in reversed(ctx.rollback):
+            undo()
+        raise
+    for jobs, run, out_list in ctx.pending:
+        run()
+        if out_list is not res:
+            for j in jobs:
+                res[j.layer_idx] = out_list[j.layer_idx]
+    execute(moves, res, N.KVC_ASC, N.KVC_ALGO_SORT)
+    return res
+
+
+def _dest_moves(kvl, res, dests, ctx):
+    """Copy-only jobs for the layers of a call with `out` that came back as the input or as a
+    slice of it (an "inplace" layer that is already at the front needs none); zero-length results
+    are written into `res` directly."""
+    moves = []
+    for i, (inp, r) in enumerate(zip(kvl, res)):
+        d = dests[i]
+        if d is None or i in ctx.done:
+            continue
+        k, v = inp
+        if r is inp or (r[0] is k and r[1] is v):
+            if d == "inplace":
+                continue  # left alone: the same objects
+            start, n = 0, k.size(2)
+        else:
+            sl = _slice_of(inp, r)
+            if sl is None:
+                raise RuntimeError(f"layer {i}: the method returned tensors that are neither its "
+                                   "input, a slice of it nor an engine output; `out` cannot place them")
+            start, n = sl
+            if d == "inplace" and start == 0:
+                continue  # already the front view
+        kd, vd = (k, v) if d == "inplace" else d
+        if n == 0:
+            res[i] = (kd.narrow(2, 0, 0), vd.narrow(2, 0, 0))
+            continue
+        moves.append(Segments(i, k, v, tail_start=start, tail_len=n, k_dest=kd, v_dest=vd,
+                              dest_checked=True))
+    return moves

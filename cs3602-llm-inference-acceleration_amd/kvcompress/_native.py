@@ -44,6 +44,12 @@ LAYER_DTYPE = np.dtype([
 ])
 assert LAYER_DTYPE.itemsize == 136
 
+# struct kvc_dest (include/kvc.h: caller-provided destinations) -- 56 bytes
+DEST_DTYPE = np.dtype([
+    ("k_stride", "<i8", (3,)), ("v_stride", "<i8", (3,)), ("in_place", "<i4"), ("reserved", "<i4"),
+])
+assert DEST_DTYPE.itemsize == 56
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -82,7 +88,7 @@ class PlanInfo(ctypes.Structure):
 EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_status_string",
            "kvc_source_digest",
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
-           "kvc_heavy_hitters", "kvc_debug_select_capacity")
+           "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest")
 
 _lib = None
 
@@ -113,6 +119,15 @@ def lib():
     L.kvc_plan.argtypes = [ctypes.POINTER(Params), vp, i32, ctypes.POINTER(PlanInfo)]
     L.kvc_launch.restype = i32
     L.kvc_launch.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
+    # additive within ABI 4: a swapped-in library (KVC_LIB) built before them lacks the two
+    # destination entries; plan_dest / launch_dest then raise
+    if hasattr(L, "kvc_plan_dest"):
+        L.kvc_plan_dest.restype = i32
+        L.kvc_plan_dest.argtypes = [ctypes.POINTER(Params), vp, vp, i32,
+                                    ctypes.POINTER(PlanInfo)]
+        L.kvc_launch_dest.restype = i32
+        L.kvc_launch_dest.argtypes = [ctypes.POINTER(Params), vp, vp, i32, vp, ctypes.c_size_t,
+                                      vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -155,6 +170,32 @@ def plan(params, table):
 def launch(params, table, ws_ptr, ws_bytes, stream_ptr):
     return lib().kvc_launch(ctypes.byref(params), table.ctypes.data, len(table), ws_ptr, ws_bytes,
                             stream_ptr)
+
+
+def _need_dest_entries():
+    if not hasattr(lib(), "kvc_plan_dest"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_plan_dest / kvc_launch_dest (built "
+                                 "before destinations); destinations need the current library")
+
+
+def plan_dest(params, table, dests):
+    """kvc_plan_dest: `dests` is a DEST_DTYPE array, one entry per layer, or None (= kvc_plan)."""
+    info = PlanInfo()
+    assert dests is None or (dests.dtype == DEST_DTYPE and len(dests) == len(table))
+    _need_dest_entries()
+    rc = lib().kvc_plan_dest(ctypes.byref(params), table.ctypes.data,
+                             dests.ctypes.data if dests is not None else None, len(table),
+                             ctypes.byref(info))
+    return rc, info
+
+
+def launch_dest(params, table, dests, ws_ptr, ws_bytes, stream_ptr):
+    """kvc_launch_dest (dests None = kvc_launch)."""
+    assert dests is None or (dests.dtype == DEST_DTYPE and len(dests) == len(table))
+    _need_dest_entries()
+    return lib().kvc_launch_dest(ctypes.byref(params), table.ctypes.data,
+                                 dests.ctypes.data if dests is not None else None, len(table),
+                                 ws_ptr, ws_bytes, stream_ptr)
 
 
 def attn_accumulate(params, table, stream_ptr):

@@ -228,6 +228,7 @@ def _run_hh(mgr, rows, out_ptr, out_stride, stream):
     N.check(rc, "kvc_heavy_hitters")
 
 
+@E.with_out
 @E.status_checked
 def h2o_attention_compress(past_key_values, attention_scores: Optional[Tuple] = None,
                            h2o_manager: Optional[H2OAttentionManager] = None,
@@ -246,6 +247,16 @@ def h2o_attention_compress(past_key_values, attention_scores: Optional[Tuple] = 
             return out
     total_cache_size = start_size + heavy_hitter_size + recent_size
     if h2o_manager is not None and attention_scores is not None:
+        if E.dest_call_active():
+            # a call with `out` checks its destinations after this method has run and before
+            # anything is written to K / V: if a check fails, the manager gets its state back
+            # (update_attention_scores replaces the accumulations, it does not write into them)
+            saved = (dict(h2o_manager.accumulated_attention), dict(h2o_manager.token_positions),
+                     h2o_manager.current_seq_len)
+
+            def undo(m=h2o_manager):
+                m.accumulated_attention, m.token_positions, m.current_seq_len = saved
+            E.on_dest_error(undo)
         h2o_manager.update_attention_scores(attention_scores, skip_layers)
     hh_jobs, host_jobs, norm_jobs = [], [], []  # (Segments, hh row | host indices)
     for layer_idx, (keys, values) in enumerate(past_key_values):
@@ -371,8 +382,8 @@ def _replay_step(kvl, attention_scores, mgr, start_size, heavy_hitter_size, rece
     update_attention_scores would, or None when the step takes the Python path (no host module,
     a timer or recording active, a first sighting, or a shape outside _plan_step's case)."""
     hm = E.host_module() if replay_steps else None
-    if hm is None or E._timer is not None or E._recording is not None:
-        return None
+    if hm is None or E._timer is not None or E._recording is not None or E.dest_call_active():
+        return None  # (a call with destinations, `out`, takes the Python path)
     if not isinstance(attention_scores, (tuple, list)):
         return None
     accs = [mgr.accumulated_attention.get(i) for i in range(len(attention_scores))]

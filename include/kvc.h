@@ -195,8 +195,8 @@ int kvc_max_zone_len(void);
 const char* kvc_status_string(int status);
 /* SHA-256 (hex) of the sources this library was compiled from (csrc/kvc.hip, then the headers it
  * includes -- kvc_common.h, kvc_serial.h, kvc_device_util.h, kvc_score.h, kvc_snapkv_keys.h,
- * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h -- then include/kvc.h, in that
- * order), or "unknown" for builds that do not set it --
+ * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h -- then
+ * include/kvc.h, in that order), or "unknown" for builds that do not set it --
  * lets a caller (and tests/test_abi.py) check that a shipped binary matches its source tree. */
 const char* kvc_source_digest(void);
 
@@ -213,6 +213,62 @@ int kvc_launch(const kvc_params_t* params, const kvc_layer_t* layers, int num_la
 /* Convenience: kvc_plan + kvc_launch.  `layers` is updated in place. */
 int kvc_compress(const kvc_params_t* params, kvc_layer_t* layers, int num_layers,
                  void* workspace, size_t workspace_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Caller-provided destinations (additive within ABI 4: kvc_layer_t and kvc_params_t are
+ * unchanged; a library without these two entries does not export them).
+ *
+ * kvc_dest_t says where one layer's result goes.  Strided destination (in_place == 0): the
+ * layer's k_out / v_out are the bases of views [batch, heads, S_d, head_dim] with S_d >= n_out,
+ * last dim contiguous, the other three dims with the element strides given here (K's and V's
+ * independent; the inputs' rules: 16-byte aligned pointers, strides of dims larger than 1
+ * multiples of 16 bytes -- the seq dim counts as larger than 1 when n_out > 1 -- else
+ * KVC_E_ALIGN).  The library writes rows [0, n_out) of every (b, h) row and no other byte.  The
+ * byte span of the K destination and of the V destination must not intersect the byte span of
+ * the same layer's K source or V source (KVC_E_ARG).  A span is [base, base + sum over the three
+ * dims of (size - 1) * stride * element size + one row's bytes), sized with n_out for a
+ * destination and seq_len for a source: the check is conservative (it refuses, e.g., a
+ * destination interleaved with its own source inside one fused buffer).  Overlap between
+ * DIFFERENT layers of a call -- a destination of one with a source or a destination of another
+ * -- is not checked: that they are disjoint is the caller's promise.
+ *
+ * In place (in_place == 1): the destination is the layer's own input -- k_out == k, v_out == v
+ * and the strides here equal the layer's k_stride / v_stride (KVC_E_ARG otherwise).  After the
+ * call rows [0, n_out) of every (b, h) row of K and V hold the compressed sequence; rows
+ * [n_out, S) and all bytes outside the written rows stay untouched.  Allowed only when the row
+ * map is strictly increasing with source row >= output row: sink_len <= zone_start when
+ * n_select > 0, and, when tail_len > 0, zone_start + zone_len <= tail_start and
+ * sink_len <= tail_start (KVC_E_ARG otherwise); caller-provided indices must be ascending (as
+ * the index region's contract says anyway).  Every stride of a dim larger than 1 must be
+ * non-zero (an expanded batch would be written twice; KVC_E_ARG).  K and V of a layer, and the
+ * layers of a call, must not share memory (the caller's promise).  Sink rows are already in
+ * place and are not touched.
+ *
+ * Values are byte-identical to kvc_launch's.  A launch with destinations runs SCORE and SELECT
+ * with the kernels of KVC_FLAG_SPLIT_SELECT_GATHER (SELECT writes the index region) and GATHER
+ * with a copy kernel of its own, which orders an in-place row's loads before its stores; phases
+ * may be launched separately as with kvc_launch.  KVC_FLAG_GATHER_FIXED / _SELECTED are refused
+ * with destinations (KVC_E_ARG).  Layers with n_out == 0 are exempt from the destination checks.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct kvc_dest {
+  int64_t k_stride[3];  /* element strides of k_out's batch, heads, seq dims */
+  int64_t v_stride[3];
+  int32_t in_place;     /* 0 or 1 (else KVC_E_ARG) */
+  int32_t reserved;     /* 0 (else KVC_E_ARG) */
+} kvc_dest_t;           /* 56 bytes */
+
+/* kvc_plan with destinations: dests[i] belongs to layers[i].  dests == NULL behaves exactly like
+ * kvc_plan.  With dests it validates them as described above, and fills the same layer fields
+ * and the same kvc_plan_info_t as kvc_plan (the workspace layout does not depend on
+ * destinations).  Pure host function. */
+int kvc_plan_dest(const kvc_params_t* params, kvc_layer_t* layers, const kvc_dest_t* dests,
+                  int num_layers, kvc_plan_info_t* info);
+
+/* kvc_launch with destinations (dests == NULL: exactly kvc_launch).  Re-validates table and
+ * destinations as kvc_plan_dest does; the kernels receive both by value. */
+int kvc_launch_dest(const kvc_params_t* params, const kvc_layer_t* layers,
+                    const kvc_dest_t* dests, int num_layers, void* workspace,
+                    size_t workspace_bytes, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |
