@@ -344,7 +344,8 @@ class _PlanCache:
     zero), kvc_plan_info, the workspace and the params.  A workspace is reused only by calls on
     the SAME stream, which are ordered behind the kernels that used it before.  Calls with
     caller-provided indices (strategy="random") are not cached: their workspace holds per-call
-    data.
+    data.  A call inside a CUDA graph capture may take its table from here but never its
+    workspace, and adds no entry ("CUDA graphs").
 
     Memory: a shape is cached on its SECOND sighting (a one-off call -- a prefill, a decode step
     whose S grows every token -- keeps no workspace), at most `capacity` entries and `max_bytes`
@@ -404,9 +405,23 @@ def status_word(device):
     Read it with device_status()."""
     w = _status_words.get(device)
     if w is None:
+        _not_while_capturing("status word", device)
         w = _status_words[device] = _new_status_word(device)
     _touch(device)
     return w
+
+
+def _not_while_capturing(what, device):
+    """The engine's per-device objects (the status word, the side stream and its events) are made
+    on first use and live for the process.  Made inside a CUDA graph capture, the word would be
+    graph-pool memory that every replay zeroes again, and a stream or event creation can
+    invalidate the capture: the first engine call on a device belongs to the warm-up
+    (INTEGRATION.md, "CUDA graphs")."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            f"kvcompress (MI355X HIP engine): the first engine call on cuda:{device} came inside "
+            f"a CUDA graph capture, where its {what} cannot be created; make one eager call of "
+            "the same kind on this device (the warm-up) before capturing")
 
 
 def _touch(device):
@@ -561,13 +576,20 @@ def _run_plain(device, dtype, B, H, D, kps, vps, segs, js, out_list, order, algo
         key = (device, stream.cuda_stream, dtype, B, H, D, order, algo, split_select_gather,
                tuple(segs))
         entry = plan_cache.get(key)
+        # A captured call owns its workspace: the graph keeps the raw pointer, so it must be
+        # memory of the graph's pool (allocated during the capture), never a cached workspace
+        # that eviction or clear() can hand back to the allocator and that eager calls on this
+        # stream go on using.  The planned table template is reused; nothing is cached.
+        capturing = torch.cuda.is_current_stream_capturing()
         if entry is None:
             entry = _plan_plain(dtype, B, H, D, order, algo, segs)
             if entry is None:  # rejected by kvc_plan (e.g. misaligned): general path reports
                 _run_general(device, dtype, B, H, D, js, out_list, order, algo, False, stream)
                 return
-            if plan_cache.admit(key):
+            if not capturing and plan_cache.admit(key):
                 plan_cache.put(key, entry, int(entry[2].numel()))
+        elif capturing:
+            entry = entry[:2] + (torch.empty_like(entry[2]),) + entry[3:]
         tmpl, info, ws, p, n_outs = entry
         if _recording is not None:
             _recording.append((stream.cuda_stream, tmpl, info, ws, p, n_outs,
@@ -666,6 +688,7 @@ def side_stream(device):
     stream's work (created once; the events have no timing and no system fence)."""
     e = _side.get(device)
     if e is None:
+        _not_while_capturing("side stream", device)
         with torch.cuda.device(device):
             e = (torch.cuda.Stream(device), HipEvent(), HipEvent())
         _side[device] = e
@@ -694,14 +717,16 @@ def execute_shared(jobs: List[Segments], out_list: list, fill, overlap=False):
     for (device, dtype, B, H, D, dest), js in groups.items():
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
+            # (the per-device objects first: made on first use, which raises inside a graph
+            # capture before _build_table can enqueue a copy of a misaligned input)
+            p = _params(dtype, B, H, D, N.KVC_ASC, N.KVC_ALGO_SORT, True, shared=True)
+            side = side_stream(device) if overlap and _timer is None and not dest else None
             table, kos, vos, keep = _build_table(device, dtype, B, H, D, js, dest)
             dests = _dest_table(js, table) if dest else None
-            p = _params(dtype, B, H, D, N.KVC_ASC, N.KVC_ALGO_SORT, True, shared=True)
             rc, info = N.plan_dest(p, table, dests) if dest else N.plan(p, table)
             N.check(rc, "kvc_plan_dest" if dest else "kvc_plan")
             ws = torch.empty(max(int(info.workspace_bytes), 256), dtype=torch.uint8,
                              device=torch.device("cuda", device))
-            side = side_stream(device) if overlap and _timer is None and not dest else None
             if side is not None:
                 pf = _params(dtype, B, H, D, N.KVC_ASC, N.KVC_ALGO_SORT, True, shared=True)
                 pf.flags |= N.FLAG_GATHER_FIXED
@@ -902,9 +927,9 @@ def _run_dest(jobs, out_list, order, algo):
             raise RuntimeError("mixed external / engine-selected layers in one group")
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
+            p = _params(dtype, B, H, D, order, algo, external)  # first: see execute_shared
             table, kos, vos, keep = _build_table(device, dtype, B, H, D, js, True)
             dests = _dest_table(js, table)
-            p = _params(dtype, B, H, D, order, algo, external)
             ws, info = _upload(p, table, device, js, B, H, dests)
             _launch(p, table, ws, info, stream, p.phases, dests)
             if _timer is not None and _timer.workspaces is not None:
@@ -915,11 +940,11 @@ def _run_dest(jobs, out_list, order, algo):
 
 
 def _run_general(device, dtype, B, H, D, js, out_list, order, algo, external, stream):
+    p = _params(dtype, B, H, D, order, algo, external)  # first: see execute_shared
     table, kos, vos, keep = _build_table(device, dtype, B, H, D, js)
     # One launch (score, select, gather kernels) for every layer of the group.  (Pipelining
     # layer chunks over two streams -- score of chunk c+1 beside select of chunk c -- was
     # measured slower at 2/4/8 chunks: profiles/r01_pipeline_sweep.json.)
-    p = _params(dtype, B, H, D, order, algo, external)
     ws, info = _upload(p, table, device, js, B, H)
     _launch(p, table, ws, info, stream, p.phases)
     if _timer is not None and _timer.workspaces is not None:
@@ -1054,19 +1079,23 @@ def memoized(fn):
         except TypeError:
             return fn(kvl, *args, **kwargs)
         rec = call_memo.get(key)
+        # inside a CUDA graph capture the replay takes a workspace of the graph's own pool (see
+        # _run_plain) and a shape not recorded yet runs `fn` without being recorded
+        capturing = torch.cuda.is_current_stream_capturing()
         if rec is not None:
             memo_stats["replayed"] += 1
             if rec.n_jobs:
                 _touch(sig[4])
+            ws = torch.empty_like(rec.ws) if capturing and rec.n_jobs else rec.ws
             if rec.n_jobs and torch.cuda.current_device() != sig[4]:
                 with torch.cuda.device(sig[4]):
                     return hm.run(kvl, rec.actions, rec.table, rec.n_jobs, rec.n_outs,
-                                  ctypes_addr(rec.params), rec.ws.data_ptr(), rec.ws_bytes,
+                                  ctypes_addr(rec.params), ws.data_ptr(), rec.ws_bytes,
                                   key[5])
             return hm.run(kvl, rec.actions, rec.table, rec.n_jobs, rec.n_outs,
                           ctypes_addr(rec.params) if rec.n_jobs else 0,
-                          rec.ws.data_ptr() if rec.n_jobs else 0, rec.ws_bytes, key[5])
-        if not call_memo.admit(key):
+                          ws.data_ptr() if rec.n_jobs else 0, rec.ws_bytes, key[5])
+        if capturing or not call_memo.admit(key):
             return fn(kvl, *args, **kwargs)
         _recording = []
         try:
