@@ -39,6 +39,7 @@
 #include "kvc_gather.h"         // gather_kernel, select_gather_kernel
 #include "kvc_attn.h"           // attn_accumulate / head-sum kernels
 #include "kvc_gather_dest.h"    // gather_dest_kernel (kvc_launch_dest)
+#include "kvc_paged.h"          // score_paged_kernel, gather_paged_kernel (kvc_launch_paged)
 
 namespace kvc {
 
@@ -236,6 +237,83 @@ static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_
   return KVC_OK;
 }
 
+// kvc_plan_paged / kvc_launch_paged: plan_impl, then the page description (and the dense
+// destination, if any) of every layer with output (include/kvc.h, "Paged caches").
+// pages == nullptr: plan_dest_impl.
+static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
+                           const kvc_dest_t* dests, int nl, kvc_plan_info_t* info, bool fill) {
+  if (!pages) return plan_dest_impl(p, layers, dests, nl, info, fill);
+  int rc = plan_impl(p, layers, nl, info, fill);
+  if (rc != KVC_OK) return rc;
+  if (p->flags & (KVC_FLAG_GATHER_FIXED | KVC_FLAG_GATHER_SELECTED)) return KVC_E_ARG;
+  const int es = esize(p->dtype);
+  const int64_t rowb = (int64_t)p->head_dim * es;
+  const int64_t B = p->batch, H = p->heads;
+  // byte span [lo, hi) of a view with three stepped dims
+  const auto span = [&](const void* base, const int64_t (&size)[3], const int64_t (&st)[3],
+                        uintptr_t* lo, uintptr_t* hi) {
+    int64_t neg = 0, pos = 0;
+    for (int d = 0; d < 3; ++d) {
+      const int64_t ext = (size[d] - 1) * st[d] * es;
+      (ext < 0 ? neg : pos) += ext;
+    }
+    *lo = (uintptr_t)base + neg;
+    *hi = (uintptr_t)base + pos + rowb;
+  };
+  for (int l = 0; l < nl; ++l) {
+    const kvc_layer_t& y = layers[l];
+    const kvc_pages_t& g = pages[l];
+    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
+    if (n_out == 0) continue;
+    if (!g.block_table || ((uintptr_t)g.block_table & 3u) || g.reserved != 0 ||
+        (g.in_place != 0 && g.in_place != 1) || g.num_pages < 1 || g.page_size < 1 ||
+        g.page_size > 65536 || (g.page_size & (g.page_size - 1)))
+      return KVC_E_ARG;
+    const int64_t P = g.page_size;
+    if (g.table_stride < ((int64_t)y.seq_len + P - 1) / P) return KVC_E_ARG;
+    if (y.k_stride[0] != 0 || y.v_stride[0] != 0) return KVC_E_ARG;  // the table is the batch dim
+    // (plan_impl has checked the head and slot strides against heads > 1 / seq_len > 1)
+    if (g.num_pages > 1 && ((g.k_page_stride * es) % 16 || (g.v_page_stride * es) % 16))
+      return KVC_E_ALIGN;
+    if (g.in_place) {
+      if (y.k_out != y.k || y.v_out != y.v) return KVC_E_ARG;
+      // the row map must be strictly increasing with src(t) >= t (plan_dest_impl's rule)
+      if ((y.n_select > 0 && y.sink_len > y.zone_start) ||
+          (y.tail_len > 0 && ((int64_t)y.zone_start + y.zone_len > y.tail_start ||
+                              y.sink_len > y.tail_start)))
+        return KVC_E_ARG;
+      // a zero stride would make different logical rows one address
+      if ((H > 1 && (y.k_stride[1] == 0 || y.v_stride[1] == 0)) ||
+          (P > 1 && y.seq_len > 1 && (y.k_stride[2] == 0 || y.v_stride[2] == 0)) ||
+          (g.num_pages > 1 && (g.k_page_stride == 0 || g.v_page_stride == 0)))
+        return KVC_E_ARG;
+      continue;
+    }
+    if (!dests) continue;  // contiguous k_out / v_out
+    const kvc_dest_t& d = dests[l];
+    if (d.reserved != 0 || d.in_place != 0) return KVC_E_ARG;
+    const int64_t* ks = d.k_stride;
+    const int64_t* vs = d.v_stride;
+    if ((B > 1 && ((ks[0] * es) % 16 || (vs[0] * es) % 16)) ||
+        (H > 1 && ((ks[1] * es) % 16 || (vs[1] * es) % 16)) ||
+        (n_out > 1 && ((ks[2] * es) % 16 || (vs[2] * es) % 16)))
+      return KVC_E_ALIGN;
+    uintptr_t slo[2], shi[2], dlo[2], dhi[2];
+    const int64_t psize[3] = {g.num_pages, H, P}, dsize[3] = {B, H, n_out};
+    const int64_t kst[3] = {g.k_page_stride, y.k_stride[1], y.k_stride[2]};
+    const int64_t vst[3] = {g.v_page_stride, y.v_stride[1], y.v_stride[2]};
+    const int64_t dks[3] = {ks[0], ks[1], ks[2]}, dvs[3] = {vs[0], vs[1], vs[2]};
+    span(y.k, psize, kst, &slo[0], &shi[0]);
+    span(y.v, psize, vst, &slo[1], &shi[1]);
+    span(y.k_out, dsize, dks, &dlo[0], &dhi[0]);
+    span(y.v_out, dsize, dvs, &dlo[1], &dhi[1]);
+    for (int a = 0; a < 2; ++a)
+      for (int b = 0; b < 2; ++b)
+        if (dlo[a] < shi[b] && slo[b] < dhi[a]) return KVC_E_ARG;
+  }
+  return KVC_OK;
+}
+
 // Every launch goes through hipLaunchKernel, whose return value is this launch's own status (a
 // caller's pending HIP error is neither consumed nor reported as ours).
 template <typename... P, typename... A>
@@ -321,6 +399,49 @@ static int launch_gather_dest(const LayerChunk& T, const kvc_dest_t* dests, int 
                   dim3(kGatherThreads), 0, s, T, D, H, BH, idx, istride, shared, status);
 }
 
+// The by-value tables of a paged chunk (<= kPagedLayers layers): layers, page descriptions, and
+// the dense outputs' strides -- the caller's kvc_dest_t, or those of a contiguous k_out / v_out.
+static void fill_pages_chunk(PagesChunk* C, const kvc_params_t* p, const kvc_layer_t* layers,
+                             const kvc_pages_t* pages, const kvc_dest_t* dests, int nl) {
+  memset(C, 0, sizeof(*C));
+  memcpy(C->l, layers, (size_t)nl * sizeof(kvc_layer_t));
+  memcpy(C->p, pages, (size_t)nl * sizeof(kvc_pages_t));
+  for (int l = 0; l < nl; ++l) {
+    if (pages[l].in_place) continue;
+    if (dests) {
+      C->d[l] = dests[l];
+      continue;
+    }
+    const int64_t n = layers[l].n_out, D = p->head_dim;
+    const int64_t st[3] = {(int64_t)p->heads * n * D, n * D, D};
+    memcpy(C->d[l].k_stride, st, sizeof(st));
+    memcpy(C->d[l].v_stride, st, sizeof(st));
+  }
+}
+
+template <int DT, int NC>
+static int launch_score_paged(const PagesChunk& C, int nl, int H, int64_t tile_base,
+                              int64_t chunk_tiles, char* norms, int64_t nstride, uint32_t* tmax,
+                              uint32_t* status, hipStream_t s) {
+  constexpr int per_wg = score_waves(NC);  // one tile per wave
+  const unsigned grid = (unsigned)((chunk_tiles + per_wg - 1) / per_wg);
+  return launch_k(score_paged_kernel<DT, NC>, dim3(grid), dim3(per_wg * 64), 0, s, C, nl, H,
+                  tile_base, chunk_tiles, norms, nstride, tmax, nstride / kTile, status);
+}
+
+// GATHER of a paged launch: grid as launch_gather_dest's (an in-place row is one workgroup's)
+template <int DT, int NC>
+static int launch_gather_paged(const PagesChunk& C, int nl, int H, int BH, const int32_t* idx,
+                               int64_t istride, int shared, uint32_t* status, hipStream_t s) {
+  int64_t work = 0;  // longest output copied by token blocks
+  for (int l = 0; l < nl; ++l)
+    if (!C.p[l].in_place && C.l[l].n_out > work) work = C.l[l].n_out;
+  constexpr int rows_per = dest_pass_rows(NC);
+  const int nby = work > 0 ? (int)((work + rows_per - 1) / rows_per) : 1;
+  return launch_k(gather_paged_kernel<DT, NC>, dim3((unsigned)(nl * BH), (unsigned)nby),
+                  dim3(kGatherThreads), 0, s, C, H, BH, idx, istride, shared, status);
+}
+
 // SELECT over the rows of a chunk (BH rows per layer, workspace row ly->row0 + blockIdx % BH):
 // the LDS kernels (512-thread rows for zones up to kSmallZone, else 1 024-thread rows) or, for
 // zones longer than kZoneMax, the global-scratch kernels (u32 positions beyond kZoneMaxGlobal).
@@ -368,10 +489,13 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
 // calls), each kernel with the chunk's table by value.
 // dests != nullptr (kvc_launch_dest): SELECT and GATHER always as two kernels, the GATHER into the
 // layers' destinations (gather_dest_kernel).
+// pages != nullptr (kvc_launch_paged; cn <= kPagedLayers): SCORE and GATHER read K / V through the
+// layers' block tables (kvc_paged.h), SELECT as with dests.
 template <int DT, int NC>
 static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, const kvc_layer_t* layers,
                         int nl, int c0, int cn, char* w, hipStream_t s,
-                        const kvc_dest_t* dests = nullptr) {
+                        const kvc_dest_t* dests = nullptr,
+                        const kvc_pages_t* pages = nullptr) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
   const int H = p->heads, BH = p->batch * p->heads;
@@ -406,13 +530,18 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
   uint32_t* tmax = snap && !ext ? reinterpret_cast<uint32_t*>(w + tmax_offset(info, p->dtype))
                                 : nullptr;
   int rc = KVC_OK;
+  PagesChunk PC;  // filled for paged launches only
+  if (pages) fill_pages_chunk(&PC, p, layers + c0, pages + c0, dests ? dests + c0 : nullptr, cn);
   if ((p->phases & KVC_PHASE_SCORE) && tile_end > tile_base && !ext)
-    rc = launch_score<DT, NC>(T, cn, H, tile_base, tile_end - tile_base, norms, nstride, tmax, s);
+    rc = pages ? launch_score_paged<DT, NC>(PC, cn, H, tile_base, tile_end - tile_base, norms,
+                                            nstride, tmax, status, s)
+               : launch_score<DT, NC>(T, cn, H, tile_base, tile_end - tile_base, norms, nstride,
+                                      tmax, s);
   if (rc != KVC_OK) return rc;
   const int n_cap = (int)nstride;  // longest zone of the call, rounded to 64
   if ((p->phases & KVC_PHASE_SELECT) && sel && !ext) {
     const bool fuse_sg = (p->phases & KVC_PHASE_GATHER) && max_out > 0 && !stamps &&
-                         !long_zone && part == PART_ALL && !dests &&
+                         !long_zone && part == PART_ALL && !dests && !pages &&
                          !(p->flags & KVC_FLAG_SPLIT_SELECT_GATHER);
     if (fuse_sg) {  // this chunk's gather happens inside the select kernel
       const int rows = cn * BH;
@@ -459,6 +588,9 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                            long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && pages)
+    return launch_gather_paged<DT, NC>(PC, cn, H, BH, idx, istride,
+                                       (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
   if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && dests)
     return launch_gather_dest<DT, NC>(T, dests + c0, cn, H, BH, idx, istride,
                                       (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
@@ -693,21 +825,33 @@ int kvc_launch(const kvc_params_t* p, const kvc_layer_t* layers, int nl, void* w
 
 int kvc_launch_dest(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_dest_t* dests,
                     int nl, void* ws, size_t ws_bytes, kvc_stream_t stream) {
+  return kvc_launch_paged(p, layers, nullptr, dests, nl, ws, ws_bytes, stream);
+}
+
+int kvc_plan_paged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                   const kvc_dest_t* dests, int num_layers, kvc_plan_info_t* info) {
+  return kvc::plan_paged_impl(params, layers, pages, dests, num_layers, info, true);
+}
+
+int kvc_launch_paged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
+                     const kvc_dest_t* dests, int nl, void* ws, size_t ws_bytes,
+                     kvc_stream_t stream) {
   using namespace kvc;
   kvc_plan_info_t info;
-  int rc = plan_dest_impl(p, const_cast<kvc_layer_t*>(layers), dests, nl, &info, false);
+  int rc = plan_paged_impl(p, const_cast<kvc_layer_t*>(layers), pages, dests, nl, &info, false);
   if (rc != KVC_OK) return rc;
   if (nl == 0) return KVC_OK;
   if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   char* w = static_cast<char*>(ws);
   const int nc = p->head_dim * esize(p->dtype) / 16;
-  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kArgLayers) {
-    const int cn = nl - c0 < kArgLayers ? nl - c0 : kArgLayers;
+  const int step = pages ? kPagedLayers : kArgLayers;  // layers per argument chunk
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
+    const int cn = nl - c0 < step ? nl - c0 : step;
     rc = with_dtype(p->dtype, [&](auto dt) {
       return with_nc(nc, [&](auto ncv) {
         return launch_chunk<decltype(dt)::value, decltype(ncv)::value>(p, info, layers, nl, c0,
-                                                                       cn, w, s, dests);
+                                                                       cn, w, s, dests, pages);
       });
     });
   }

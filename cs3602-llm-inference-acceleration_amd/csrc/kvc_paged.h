@@ -1,0 +1,307 @@
+// kvc_paged.h -- paged K/V sources (kvc_launch_paged): SCORE and GATHER of layers whose rows live
+// in a page pool addressed through a per-sequence block table (include/kvc.h, "Paged caches").
+// SELECT reads the workspace only and runs the kernels of kvc_select.h unchanged.
+#pragma once
+
+#include "kvc_gather_dest.h"
+#include "kvc_score.h"
+
+namespace kvc {
+
+// Paged launches run in chunks of kPagedLayers: a chunk's layers, page tables and destinations
+// travel by value in ONE struct of 7.5 KiB -- below the 12.2 KiB (LayerChunk + DestChunk) that
+// kvc_launch_dest's copy kernel is known to launch with.  (Three 64-entry tables would be 15 KiB
+// of kernel arguments; no host-to-device table copy instead: see kArgLayers.)
+constexpr int kPagedLayers = 32;
+struct PagesChunk {
+  kvc_layer_t l[kPagedLayers];
+  kvc_pages_t p[kPagedLayers];
+  kvc_dest_t d[kPagedLayers];  // dense outputs: their strides (a contiguous k_out's as well)
+};
+
+// Address arithmetic of one (layer, b, h) row of a paged K or V: logical row s lives at
+//   pool + (table[s >> lg] * page_stride + h * stride[1] + (s & (P - 1)) * stride[2]) * esz.
+// A page id outside [0, num_pages) is clamped for loads (KVC_DEV_INDEX_RANGE); `ok` says whether
+// it was in range (an in-place store through a bad id is dropped).
+struct PageRow {
+  const int32_t* tab;  // block_table + b * table_stride
+  int lg, mask, np;
+  __device__ __forceinline__ PageRow(const kvc_pages_t* pg, int b)
+      : tab(pg->block_table + (int64_t)b * pg->table_stride),
+        lg(31 - __builtin_clz((unsigned)pg->page_size)),
+        mask(pg->page_size - 1),
+        np(pg->num_pages) {}
+  // page id of logical row s, clamped; *ok = it was in range
+  __device__ __forceinline__ int page(int s, bool* ok) const {
+    const int id = tab[s >> lg];
+    *ok = id >= 0 && id < np;
+    return min(max(id, 0), np - 1);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
+// SCORE of paged keys: score_tile (kvc_score.h) with the row address of every staged token taken
+// through the block table.  Same tile structure (one wave = 64 consecutive zone tokens of one
+// (layer, b, h) row), LDS slab, FMA order, non-temporal loads, norm stores and snapkv tile
+// maxima; a tile may start anywhere in a page and span many pages or a fraction of one.  Each lane
+// stages CP (token, 16-B chunk) units per phase, of CP / gcd distinct tokens; the page id of a unit's
+// token is looked up ONCE, before the phases, and kept as the unit's row pointer.
+// ---------------------------------------------------------------------------------------------
+template <int DT, int NC>
+__device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kvc_pages_t* pg,
+                                                 int row, int tt, int H, char* wl, char* norms,
+                                                 int64_t norm_stride, uint32_t* tmax,
+                                                 int64_t tmax_stride, uint32_t* status) {
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  constexpr int CP = score_cp(NC);
+  constexpr int NPH = NC / CP;
+  constexpr int ROWB = score_rowb(CP);
+  const int lane = threadIdx.x & 63;
+  const int zlen = ly->zone_len;
+  const int b = row / H, h = row - (row / H) * H;
+  const int tok0 = tt * kTile;
+  const int ntok = min(kTile, zlen - tok0);
+  const int64_t sbytes = ly->k_stride[2] * ESZ, pbytes = pg->k_page_stride * ESZ;
+  const char* base = static_cast<const char*>(ly->k) + (int64_t)h * ly->k_stride[1] * ESZ;
+  const PageRow pr(pg, b);
+  const int s0 = ly->zone_start + tok0;
+  const char* rowp[CP];  // row pointer of the token of unit `it` (nullptr past the zone)
+  bool bad = false;
+#pragma unroll
+  for (int it = 0; it < CP; ++it) {
+    const int q = it * 64 + lane;
+    const int tok = q / CP;
+    rowp[it] = nullptr;
+    if (tok < ntok) {
+      const int s = s0 + tok;
+      bool ok;
+      const int id = pr.page(s, &ok);
+      bad |= !ok;
+      rowp[it] = base + (int64_t)id * pbytes + (int64_t)(s & pr.mask) * sbytes;
+    }
+  }
+  if (bad && status) atomicOr(status, (uint32_t)KVC_DEV_INDEX_RANGE);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ph = 0; ph < NPH; ++ph) {
+    uint4 v[CP];
+#pragma unroll
+    for (int it = 0; it < CP; ++it) {
+      const int q = it * 64 + lane;
+      const int c = q - (q / CP) * CP;
+      if (rowp[it]) {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 w = __builtin_nontemporal_load(
+            reinterpret_cast<const u32x4*>(rowp[it] + (ph * CP + c) * 16));
+        v[it] = make_uint4(w.x, w.y, w.z, w.w);
+      } else {
+        v[it] = make_uint4(0, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < CP; ++it) {
+      const int q = it * 64 + lane;
+      const int tok = q / CP, c = q - (q / CP) * CP;
+      *reinterpret_cast<uint4*>(wl + tok * ROWB + c * 16) = v[it];
+    }
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      const uint4 x = *reinterpret_cast<const uint4*>(wl + lane * ROWB + c * 16);
+      accum_chunk<DT, NC>(acc, x, ph * CP + c);
+    }
+    wave_sync();
+  }
+  uint32_t bits = 0;  // the stored norm's bits (0 for lanes past the zone)
+  if (lane < ntok) {
+    float s = acc[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) s = s + acc[j];
+    const float r = __builtin_sqrtf(s);
+    char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * ESZ;
+    if constexpr (DT != KVC_F32) {
+      bits = bits16_dt<DT>(r);
+      __builtin_nontemporal_store((uint16_t)bits, reinterpret_cast<uint16_t*>(nrow) + tok0 + lane);
+    } else {
+      bits = f32_to_bits(r);
+      __builtin_nontemporal_store(r, reinterpret_cast<float*>(nrow) + tok0 + lane);
+    }
+  }
+  if (ly->score_mode == KVC_SCORE_SNAPKV && tmax) {  // wave-uniform
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, o, 64));
+    if (lane == 0) tmax[(int64_t)(ly->row0 + row) * tmax_stride + tt] = bits;
+  }
+}
+
+template <int DT, int NC>
+__global__ void __launch_bounds__(score_waves(NC) * 64)
+    score_paged_kernel(const PagesChunk T, int nl, int H, int64_t tile_base, int64_t chunk_tiles,
+                       char* __restrict__ norms, int64_t norm_stride, uint32_t* __restrict__ tmax,
+                       int64_t tmax_stride, uint32_t* status) {
+  constexpr int CP = score_cp(NC);
+  constexpr int ROWB = score_rowb(CP);
+  constexpr int kScoreWaves = score_waves(NC);
+  __shared__ __attribute__((aligned(16))) char lds[kScoreWaves][kTile * ROWB];
+  const kvc_layer_t* L = T.l;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * kScoreWaves;
+  for (int64_t gl = (int64_t)blockIdx.x * kScoreWaves + wid; gl < chunk_tiles; gl += stride) {
+    const int64_t g = tile_base + gl;  // global tile index (kvc_plan's tile0 numbering)
+    int lo = 0, hi = nl - 1;  // largest layer with tile0 <= g
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (L[mid].tile0 <= g)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    const kvc_layer_t* ly = L + lo;
+    const int tpr = (ly->zone_len + kTile - 1) / kTile;
+    const int local = (int)(g - ly->tile0);
+    const int row = local / tpr;
+    score_paged_tile<DT, NC>(ly, T.p + lo, row, local - row * tpr, H, lds[wid], norms,
+                             norm_stride, tmax, tmax_stride, status);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// GATHER of paged sources: the rows gather_dest_kernel copies, read through the block table, into
+//   * a dense destination (kvc_pages_t.in_place == 0): b * os0 + h * os1 + t * os2 of T.d -- the
+//     layer's kvc_dest_t, or the strides of a contiguous k_out / v_out; block (row, by) copies
+//     one pass of dest_pass_rows(NC) output rows, no ordering constraint;
+//   * the pool itself (in_place == 1): output row t goes to the slot of LOGICAL row t through the
+//     same table.  gather_dest_kernel's schedule: ONE workgroup per (layer, b, h) row -- block
+//     (row, 0) -- ascending passes of consecutive output rows, and in every pass all loads have
+//     returned in every wave (s_waitcnt vmcnt(0), then the barrier) before any store.
+//
+// Why that is still a correct memmove.  The proof in kvc_gather_dest.h speaks about ROWS, not
+// addresses: the row map is strictly increasing with src(t) >= t (kvc_plan_paged applies
+// kvc_plan_dest's segment-order rule; ascending indices), so output row t overwrites only a
+// logical row that is the source of output rows <= t; a pass's stores follow all of its loads; the
+// sources of pass p+1 are logical rows above every destination of passes <= p.  What the proof
+// needs from memory is only that DIFFERENT logical rows of one (b, h) sequence are different
+// bytes.  With a block table, logical row s is (page table[s >> lg], slot s & (P-1)): distinct
+// page ids within a table row (the caller's promise) and non-zero, non-overlapping strides make
+// s -> address injective, whatever order the pages have in the pool -- a shuffled table permutes
+// addresses, not rows.  Different (b, h) rows, K and V, and layers share no written page (the
+// promise), so workgroups do not meet.  The table is only read.  Sink rows have src == dst and
+// are not touched, so pages holding only sink rows may be shared between sequences.
+// An in-place store through a page id outside [0, num_pages) is DROPPED (loads are clamped).
+// ---------------------------------------------------------------------------------------------
+template <int DT, int NC>
+__global__ void __launch_bounds__(kGatherThreads)
+    gather_paged_kernel(const PagesChunk T, int H, int BH, const int32_t* __restrict__ gidx,
+                        int64_t idx_stride, int shared, uint32_t* status) {
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  constexpr int ROWS = dest_pass_rows(NC);
+  const int li = (int)blockIdx.x / BH;
+  const kvc_layer_t* ly = T.l + li;
+  const kvc_pages_t* pg = T.p + li;
+  const kvc_dest_t* de = T.d + li;
+  const int r = (int)blockIdx.x - li * BH;
+  const int n_out = ly->n_out;
+  const bool inplace = pg->in_place != 0;
+  const int sink = ly->sink_len, nsel = ly->n_select;
+  int t_begin, t_end;
+  if (inplace) {
+    if (blockIdx.y != 0) return;
+    t_begin = sink;
+    t_end = n_out;
+  } else {
+    t_begin = (int)blockIdx.y * ROWS;
+    t_end = min(n_out, t_begin + ROWS);
+  }
+  if (t_begin >= t_end) return;
+  const int b = r / H, h = r - (r / H) * H;
+  const PageRow pr(pg, b);
+  const char* kb = static_cast<const char*>(ly->k) + (int64_t)h * ly->k_stride[1] * ESZ;
+  const char* vb = static_cast<const char*>(ly->v) + (int64_t)h * ly->v_stride[1] * ESZ;
+  const int64_t kss = ly->k_stride[2] * ESZ, vss = ly->v_stride[2] * ESZ;
+  const int64_t kps = pg->k_page_stride * ESZ, vps = pg->v_page_stride * ESZ;
+  // dense destination rows (unused in place)
+  char* ko = static_cast<char*>(ly->k_out) +
+             ((int64_t)b * de->k_stride[0] + (int64_t)h * de->k_stride[1]) * ESZ;
+  char* vo = static_cast<char*>(ly->v_out) +
+             ((int64_t)b * de->v_stride[0] + (int64_t)h * de->v_stride[1]) * ESZ;
+  const int64_t kos = de->k_stride[2] * ESZ, vos = de->v_stride[2] * ESZ;
+  // index row of (layer, b, h); KVC_FLAG_SHARED_INDEX: (layer, b)'s row serves every head
+  const int32_t* irow = gidx + (int64_t)((ly->row0 + r) / (shared ? H : 1)) * idx_stride;
+  const int zone_len = ly->zone_len, zone_start = ly->zone_start, tail_start = ly->tail_start;
+  bool bad = false;
+  for (int t0 = t_begin; t0 < t_end; t0 += ROWS) {  // ascending passes
+    const int nu = min(ROWS, t_end - t0) * NC;
+    uint4 xk[kDestIters], xv[kDestIters];
+    bool gat[kDestIters];
+    int zi[kDestIters];
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      const int t = t0 + u / NC;
+      gat[i] = u < nu && t >= sink && t < sink + nsel;
+      zi[i] = gat[i] ? irow[t - sink] : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      if (u < nu) {
+        const int t = t0 + u / NC, c = u - (u / NC) * NC;
+        int src;
+        if (t < sink) {
+          src = t;
+        } else if (gat[i]) {
+          bad |= zi[i] < 0 || zi[i] >= zone_len;  // never read outside the zone: clamp
+          src = zone_start + min(max(zi[i], 0), zone_len - 1);
+        } else {
+          src = tail_start + (t - sink - nsel);
+        }
+        bool ok;
+        const int64_t id = pr.page(src, &ok);  // one lookup per (lane, row): K and V share it
+        bad |= !ok;
+        const int slot = src & pr.mask;
+        xk[i] = *reinterpret_cast<const uint4*>(kb + id * kps + slot * kss + c * 16);
+        xv[i] = *reinterpret_cast<const uint4*>(vb + id * vps + slot * vss + c * 16);
+      }
+    }
+    if (inplace) {  // uniform over the workgroup
+      // every load of this pass has returned in this wave, then in all waves, before any store
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < kDestIters; ++i) {
+      const int u = threadIdx.x + i * kGatherThreads;
+      if (u < nu) {
+        const int t = t0 + u / NC, c = u - (u / NC) * NC;
+        uint4 a = xk[i], q = xv[i];
+        if (gat[i]) {  // torch.gather's NaN rewrite (gathered segment only)
+          a = canon_nan_dt<DT>(a);
+          q = canon_nan_dt<DT>(q);
+        }
+        char* kd;
+        char* vd;
+        bool ok = true;
+        if (inplace) {  // the slot of logical row t
+          const int64_t id = pr.page(t, &ok);
+          bad |= !ok;
+          const int slot = t & pr.mask;
+          kd = const_cast<char*>(kb) + id * kps + slot * kss;
+          vd = const_cast<char*>(vb) + id * vps + slot * vss;
+        } else {
+          kd = ko + t * kos;
+          vd = vo + t * vos;
+        }
+        if (ok) {  // a bad page id: the store is dropped, not clamped
+          typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+          __builtin_nontemporal_store(u32x4{a.x, a.y, a.z, a.w},
+                                      reinterpret_cast<u32x4*>(kd + c * 16));
+          __builtin_nontemporal_store(u32x4{q.x, q.y, q.z, q.w},
+                                      reinterpret_cast<u32x4*>(vd + c * 16));
+        }
+      }
+    }
+  }
+  if (bad && status) atomicOr(status, (uint32_t)KVC_DEV_INDEX_RANGE);
+}
+
+}  // namespace kvc

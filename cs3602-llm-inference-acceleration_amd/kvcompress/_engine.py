@@ -42,6 +42,9 @@ class Segments:
     v_dest: Optional[torch.Tensor] = None
     dest_checked: bool = False  # dest_call() has run _check_dest_tensors on this destination
     dest_verified: bool = False  # ... and _check_dest: the launch does not repeat it
+    # compress_paged: the layer's PagedKV.  keys / values are then stand-ins of the layer's shape
+    # (nothing is read from them) and the job is launched by paged.run_jobs (kvc_launch_paged)
+    paged: Optional[object] = None
 
 
 _SUPPORTED = {torch.bfloat16: N.KVC_BF16, torch.float16: N.KVC_F16, torch.float32: N.KVC_F32}
@@ -237,6 +240,10 @@ def execute(jobs: List[Segments], out_list: list, order: int, algo: int):
                                  f"{j.zone_len}); use the reference policy for longer zones")
     if _defer(jobs, lambda: execute(jobs, out_list, order, algo), out_list):
         return  # a call with `out`: dest_call() launches once every destination is checked
+    if jobs[0].paged is not None:  # compress_paged's jobs, checked by it
+        from .paged import run_jobs
+        run_jobs(jobs, order, algo)
+        return
     jobs, dest_jobs = _split_dest_jobs(jobs)
     for j in dest_jobs:  # jobs that carry destinations of their own (no `out` call in progress)
         _check_dest(j)
@@ -288,10 +295,13 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H, dests=None):
+def _upload(params, table, device, js, B, H, dests=None, pages=None):
     """Plan one table and allocate its workspace.  The table itself travels in the kernels'
     arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    if dests is None:
+    if pages is not None:
+        rc, info = N.plan_paged(params, table, pages, dests)
+        N.check(rc, "kvc_plan_paged")
+    elif dests is None:
         rc, info = N.plan(params, table)
         N.check(rc, "kvc_plan")
     else:
@@ -309,7 +319,7 @@ def _upload(params, table, device, js, B, H, dests=None):
     return ws, info
 
 
-def _launch(params, table, ws, info, stream, phases, dests=None):
+def _launch(params, table, ws, info, stream, phases, dests=None, pages=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
@@ -320,7 +330,10 @@ def _launch(params, table, ws, info, stream, phases, dests=None):
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        if dests is None:
+        if pages is not None:
+            rc = N.launch_paged(params, table, pages, dests, ws.data_ptr(),
+                                int(info.workspace_bytes), stream.cuda_stream)
+        elif dests is None:
             rc = N.launch(params, table, ws.data_ptr(), int(info.workspace_bytes),
                           stream.cuda_stream)
         else:
@@ -328,7 +341,8 @@ def _launch(params, table, ws, info, stream, phases, dests=None):
                                stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch" if dests is None else "kvc_launch_dest")
+        N.check(rc, "kvc_launch_paged" if pages is not None else
+                "kvc_launch" if dests is None else "kvc_launch_dest")
         if _timer is not None:
             _timer.records.append((name, a, b))
     params.phases = saved

@@ -50,6 +50,14 @@ DEST_DTYPE = np.dtype([
 ])
 assert DEST_DTYPE.itemsize == 56
 
+# struct kvc_pages (include/kvc.h: paged caches) -- 48 bytes
+PAGES_DTYPE = np.dtype([
+    ("block_table", "<u8"), ("table_stride", "<i8"), ("k_page_stride", "<i8"),
+    ("v_page_stride", "<i8"), ("page_size", "<i4"), ("num_pages", "<i4"), ("in_place", "<i4"),
+    ("reserved", "<i4"),
+])
+assert PAGES_DTYPE.itemsize == 48
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -88,7 +96,8 @@ class PlanInfo(ctypes.Structure):
 EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_status_string",
            "kvc_source_digest",
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
-           "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest")
+           "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
+           "kvc_plan_paged", "kvc_launch_paged")
 
 _lib = None
 
@@ -128,6 +137,13 @@ def lib():
         L.kvc_launch_dest.restype = i32
         L.kvc_launch_dest.argtypes = [ctypes.POINTER(Params), vp, vp, i32, vp, ctypes.c_size_t,
                                       vp]
+    if hasattr(L, "kvc_plan_paged"):  # additive within ABI 4, like the destination entries
+        L.kvc_plan_paged.restype = i32
+        L.kvc_plan_paged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32,
+                                     ctypes.POINTER(PlanInfo)]
+        L.kvc_launch_paged.restype = i32
+        L.kvc_launch_paged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32, vp,
+                                       ctypes.c_size_t, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -196,6 +212,37 @@ def launch_dest(params, table, dests, ws_ptr, ws_bytes, stream_ptr):
     return lib().kvc_launch_dest(ctypes.byref(params), table.ctypes.data,
                                  dests.ctypes.data if dests is not None else None, len(table),
                                  ws_ptr, ws_bytes, stream_ptr)
+
+
+def _need_paged_entries():
+    if not hasattr(lib(), "kvc_plan_paged"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_plan_paged / kvc_launch_paged (built "
+                                 "before paged caches); paged caches need the current library")
+
+
+def _opt(a, dtype, n):
+    assert a is None or (a.dtype == dtype and len(a) == n)
+    return a.ctypes.data if a is not None else None
+
+
+def plan_paged(params, table, pages, dests=None):
+    """kvc_plan_paged: `pages` is a PAGES_DTYPE array, one entry per layer, or None (=
+    kvc_plan_dest); `dests` a DEST_DTYPE array or None."""
+    info = PlanInfo()
+    _need_paged_entries()
+    rc = lib().kvc_plan_paged(ctypes.byref(params), table.ctypes.data,
+                              _opt(pages, PAGES_DTYPE, len(table)),
+                              _opt(dests, DEST_DTYPE, len(table)), len(table), ctypes.byref(info))
+    return rc, info
+
+
+def launch_paged(params, table, pages, dests, ws_ptr, ws_bytes, stream_ptr):
+    """kvc_launch_paged (pages None = kvc_launch_dest)."""
+    _need_paged_entries()
+    return lib().kvc_launch_paged(ctypes.byref(params), table.ctypes.data,
+                                  _opt(pages, PAGES_DTYPE, len(table)),
+                                  _opt(dests, DEST_DTYPE, len(table)), len(table), ws_ptr,
+                                  ws_bytes, stream_ptr)
 
 
 def attn_accumulate(params, table, stream_ptr):

@@ -195,8 +195,8 @@ int kvc_max_zone_len(void);
 const char* kvc_status_string(int status);
 /* SHA-256 (hex) of the sources this library was compiled from (csrc/kvc.hip, then the headers it
  * includes -- kvc_common.h, kvc_serial.h, kvc_device_util.h, kvc_score.h, kvc_snapkv_keys.h,
- * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h -- then
- * include/kvc.h, in that order), or "unknown" for builds that do not set it --
+ * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h,
+ * kvc_paged.h -- then include/kvc.h, in that order), or "unknown" for builds that do not set it --
  * lets a caller (and tests/test_abi.py) check that a shipped binary matches its source tree. */
 const char* kvc_source_digest(void);
 
@@ -269,6 +269,79 @@ int kvc_plan_dest(const kvc_params_t* params, kvc_layer_t* layers, const kvc_des
 int kvc_launch_dest(const kvc_params_t* params, const kvc_layer_t* layers,
                     const kvc_dest_t* dests, int num_layers, void* workspace,
                     size_t workspace_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Paged caches (additive within ABI 4: kvc_layer_t, kvc_params_t and kvc_dest_t are unchanged; a
+ * library without these two entries does not export them).
+ *
+ * kvc_pages_t says that one layer's K and V live in a page pool addressed through a block table,
+ * as the paged-attention caches of serving stacks do.  The layer's k / v are the pool bases
+ * (page 0), and logical row s of (b, h) is read at
+ *     base + (block_table[b * table_stride + (s >> log2 P)] * page_stride + h * stride[1]
+ *             + (s & (P - 1)) * stride[2]) * element size          (P = page_size)
+ * so the layer's stride[1] / stride[2] step over the heads and the slots INSIDE a page and the
+ * table replaces the batch stride: stride[0] must be 0 (KVC_E_ARG).  K's and V's strides and page
+ * strides are independent: one description covers a pool stored [N, P, H, D] and one stored
+ * [N, H, P, D].  The inputs' alignment rules hold (16-byte aligned pointers, strides of dims
+ * larger than 1 multiples of 16 bytes, else KVC_E_ALIGN; the page stride counts as a dim larger
+ * than 1 when num_pages > 1).  block_table NULL or not 4-byte aligned, table_stride smaller than
+ * ceil(seq_len / page_size), a page_size that is not a power of two in [1, 65536], num_pages < 1,
+ * in_place other than 0 / 1 or reserved != 0 give KVC_E_ARG.  All address arithmetic is 64-bit:
+ * offsets beyond 2^32 bytes are fine.  With `pages`, every layer of the call is paged; pages[i]
+ * belongs to layers[i].
+ *
+ * Output of a paged layer, one of three:
+ *   (a) in_place == 0, dests == NULL: contiguous k_out / v_out, as with kvc_launch.
+ *   (b) in_place == 0, dests[i]: a strided dense destination under kvc_dest_t's rules
+ *       (dests[i].in_place must be 0).  Its byte span must not meet the K or V pool's span --
+ *       [base, base + ((num_pages - 1) * page_stride + (heads - 1) * stride[1] + (P - 1) *
+ *       stride[2]) * element size + one row's bytes) for non-negative strides; conservative as
+ *       above (KVC_E_ARG).
+ *   (c) in_place == 1: k_out == k and v_out == v (KVC_E_ARG otherwise); dests[i] is not read.
+ *       Output row t is written to the slot of LOGICAL row t through the same table, so the
+ *       compressed sequence ends up in the sequence's leading pages and the caller can free the
+ *       pages from ceil(n_out / P) on.  The segment-order rules of kvc_dest_t's in-place contract
+ *       apply unchanged; strides of dims larger than 1 must be non-zero.  Sink rows are not
+ *       touched; rows [n_out, seq_len) and every pool byte that is not a written row keep their
+ *       contents.  The caller promises that the page ids of one table row are distinct, that
+ *       different batch rows, K and V, and different layers share no page that is written, and
+ *       that the table is not modified while the call runs.  Pages that hold only sink rows are
+ *       never written and so may be shared between sequences (a shared prefix).
+ *
+ * Values are byte-identical to kvc_launch on the dense tensor the table describes.  SCORE and
+ * GATHER run kernels of their own that differ from the dense ones in address arithmetic only;
+ * SELECT is the kernels of KVC_FLAG_SPLIT_SELECT_GATHER (it reads the workspace only).  Phases may
+ * be launched separately under the contract above; external_index and KVC_FLAG_SHARED_INDEX work;
+ * KVC_FLAG_GATHER_FIXED / _SELECTED are refused (KVC_E_ARG).  Plan info and workspace layout are
+ * kvc_plan's for the same table.  Layers with n_out == 0 are exempt from the page checks.
+ *
+ * Device safety: a page id outside [0, num_pages) is clamped for loads and KVC_DEV_INDEX_RANGE is
+ * ORed into the status word; an in-place store through such an id is dropped, not clamped.
+ * The table is device data read when the kernels run: a replay of a captured launch follows the
+ * table's contents at replay time.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct kvc_pages {
+  const int32_t* block_table; /* device memory: page id of logical page p of batch row b at
+                                 block_table[b * table_stride + p]                          */
+  int64_t table_stride;       /* int32 entries per batch row, >= ceil(seq_len / page_size)   */
+  int64_t k_page_stride;      /* elements between consecutive pages of the K pool            */
+  int64_t v_page_stride;
+  int32_t page_size;          /* tokens per page: a power of two, 1 .. 65536                 */
+  int32_t num_pages;          /* pages in the pool, >= 1                                     */
+  int32_t in_place;           /* 0 or 1                                                      */
+  int32_t reserved;           /* 0                                                           */
+} kvc_pages_t;                /* 48 bytes */
+
+/* kvc_plan_dest for paged layers.  pages == NULL behaves exactly like kvc_plan_dest.  Fills the
+ * same layer fields and the same kvc_plan_info_t as kvc_plan.  Pure host function. */
+int kvc_plan_paged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                   const kvc_dest_t* dests, int num_layers, kvc_plan_info_t* info);
+
+/* kvc_launch_dest for paged layers (pages == NULL: exactly kvc_launch_dest).  Re-validates as
+ * kvc_plan_paged does; the kernels receive the three tables by value. */
+int kvc_launch_paged(const kvc_params_t* params, const kvc_layer_t* layers,
+                     const kvc_pages_t* pages, const kvc_dest_t* dests, int num_layers,
+                     void* workspace, size_t workspace_bytes, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |
