@@ -404,6 +404,15 @@ __device__ __forceinline__ bool select_body(const kvc_layer_t* __restrict__ ly, 
   KVC_STAMP(0);
   const int n = ly->zone_len;
   const int k = ly->n_select;
+  if constexpr (!TO_LDS) {
+    // A row that keeps its whole zone uses none of the arrays, and its zone may be longer than
+    // n_cap: the plan sizes that by the selecting layers alone and accepts a kept zone of any
+    // length.  Its index row is the identity.
+    if (k > 0 && k >= n) {
+      for (int i = threadIdx.x; i < n; i += NT) out[i] = i;
+      return true;
+    }
+  }
   if (n > MAXN || n > n_cap) {  // a dispatch bug, never silent: flag it, select nothing
     if (threadIdx.x == 0 && status) atomicOr(status, (uint32_t)KVC_DEV_SELECT_BOUNDS);
     return false;
@@ -785,18 +794,18 @@ __global__ void __launch_bounds__(kSelThreads)
   const kvc_layer_t* ly = T.l + blockIdx.x / BH;
   const int row = ly->row0 + (int)(blockIdx.x % BH);
   const int n = ly->zone_len, k = ly->n_select;
+  int32_t* out = out_idx + (int64_t)row * idx_stride;
+  if (k > 0 && k >= n) {  // keeps its whole zone: no scratch, any length (as in select_body)
+    for (int i = threadIdx.x; i < n; i += kSelThreads) out[i] = i;
+    return;
+  }
   if (n > n_cap || n > kZoneMaxLong) {
     if (threadIdx.x == 0 && status) atomicOr(status, (uint32_t)KVC_DEV_SELECT_BOUNDS);
     return;
   }
   if (k <= 0 || n <= 0) return;
   const char* nrow = norms + (int64_t)row * norm_stride * ESZ;
-  int32_t* out = out_idx + (int64_t)row * idx_stride;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (k >= n) {
-    for (int i = tid; i < n; i += kSelThreads) out[i] = i;
-    return;
-  }
   char* base = scratch + (int64_t)row * scratch_row_bytes;
   KeyT* key = reinterpret_cast<KeyT*>(base);
   uint32_t* idx = reinterpret_cast<uint32_t*>(base + (size_t)n_cap * sizeof(KeyT));

@@ -61,7 +61,9 @@ def make_inputs(case, values="data"):
         shape = tuple(L["shape"])
         K = prng.gen_keys(L["kseed"], shape, case["dtype"], L.get("variant", "normal"))
         assert sha(K) == case["input_sha"][li], "PRNG drift: regenerated K differs from fixture"
-        V = (prng.gen_values(L["kseed"], shape, case["dtype"]) if values == "data"
-             else prng.encode_positions(shape, case["dtype"]))
+        V = (prng.gen_values(L["kseed"], shape, case["dtype"], L.get("vvariant", "normal"))
+             if values == "data" else prng.encode_positions(shape, case["dtype"]))
+        if values == "data" and "v_input_sha" in case:
+            assert sha(V) == case["v_input_sha"][li], "PRNG drift: regenerated V differs from fixture"
         out.append((K, V))
     return out

@@ -16,7 +16,9 @@ The reference is imported from /root/reference (read-only); nothing of it is cop
                    in parts under 1 MiB each, like the prims: npz_parts.py)
   prims.json / prims.*.npz - torch.norm / argsort / topk outputs on tie-heavy rows, and the
                    snapkv_lite scoring tensors (max + 1e-6, scores, pooled) per dtype
-Inputs are regenerated from tests/golden/prng.py recipes (hashes stored to detect drift).
+Inputs are regenerated from tests/golden/prng.py recipes (hashes stored to detect drift: of K for
+every case, of V too -- `v_input_sha` -- for the cases generated since layer recipes can carry a
+`vvariant`, the variant of prng.gen_values).
 """
 import hashlib
 import json
@@ -61,7 +63,7 @@ def make_layers(case, values="data"):
         shape = tuple(L["shape"])
         K = prng.gen_keys(L["kseed"], shape, case["dtype"], L.get("variant", "normal"))
         if values == "data":
-            V = prng.gen_values(L["kseed"], shape, case["dtype"])
+            V = prng.gen_values(L["kseed"], shape, case["dtype"], L.get("vvariant", "normal"))
         else:
             V = prng.encode_positions(shape, case["dtype"])
         out.append((K, V))
@@ -85,8 +87,13 @@ def add(method, kwargs, dtype, layers, tag=""):
                   "layers": layers})
 
 
-def L(shape, seed, variant="normal"):
-    return {"shape": list(shape), "kseed": seed, "variant": variant}
+def L(shape, seed, variant="normal", vvariant=None):
+    """One layer's recipe; `vvariant` (prng.gen_values' variant) is stored only when given, so the
+    recipes of the earlier cases stay as they were."""
+    r = {"shape": list(shape), "kseed": seed, "variant": variant}
+    if vvariant is not None:
+        r["vvariant"] = vvariant
+    return r
 
 
 def build_cases():
@@ -281,6 +288,52 @@ def build_cases():
     add("fix_size_l2", {"fix_kv_size": 512, "keep_ratio": 0.0, "strategy": "keep_low",
                         "skip_layers": []}, "fp32", [L((1, 8, 16384, 128), s + 403, "few")],
         "headline_fp32_ties")
+    # ---- NaN payloads (tests/test_nan_payload.py): "payload" keys (non-canonical NaNs of both
+    # signs in every 9th row) and "patterns" values (every NaN bit pattern of the dtype, in both
+    # halves of a word).  A NaN norm sorts last ascending, so the selections keep nearly the
+    # whole zone (or its largest norms first): the gathered segment then holds NaN key rows and
+    # enough value rows for every pattern.  No registered method selects a whole zone
+    # (n_select == zone_len), so that layer shape has no golden; the GPU tests reach it through
+    # the C ABI. ----
+    def P(shape, seed):
+        return L(shape, seed, "payload", "patterns")
+
+    big = (2, 3, 1500, 64)
+    for dt in ("bf16", "fp16"):
+        t = "nan"
+        add("fix_size_l2", {"fix_kv_size": 1400, "keep_ratio": 0.25, "strategy": "keep_low",
+                            "skip_layers": []}, dt, [P(big, s + 500), P((2, 3, 1450, 64), s + 501)], t)
+        add("fix_size_l2", {"fix_kv_size": 1200, "keep_ratio": 0.25, "strategy": "keep_high",
+                            "skip_layers": []}, dt, [P(big, s + 502)], t + "_keep_high")
+        add("l2_compress", {"keep_ratio": 0.95, "prune_after": 100, "skip_layers": []}, dt,
+            [P(big, s + 503)], t + "_all_gathered")
+        add("streaming_llm", {"start_size": 4, "recent_size": 1020}, dt, [P(big, s + 504)], t)
+        add("recent_only", {"window_size": 512, "skip_layers": []}, dt, [P(big, s + 505)], t)
+        add("h2o_l2", {"start_size": 4, "heavy_hitter_size": 1200, "recent_size": 200}, dt,
+            [P(big, s + 506)], t)
+        add("snapkv_lite", {"observation_window": 32, "keep_size": 1200, "pooling_kernel": 5}, dt,
+            [P(big, s + 507)], t)
+        add("pyramid_kv", {"base_size": 1450, "layer_decay": 1.0}, dt,
+            [P(big, s + 508), P(big, s + 509)], t)
+        add("adaptive_l2", {"target_size": 1450, "soft_limit": 256, "hard_limit": 1400,
+                            "keep_ratio_min": 0.97, "keep_ratio_max": 0.97}, dt,
+            [P(big, s + 510), P((2, 3, 1300, 64), s + 511)], t)
+        add("evict_for_space", {"num_coming": 1, "start_size": 4, "recent_size": 508}, dt,
+            [P(big, s + 512)], t)
+    for m, kw in (("fix_size_l2", {"fix_kv_size": 1400, "keep_ratio": 0.25, "strategy": "keep_low",
+                                   "skip_layers": []}),
+                  ("h2o_l2", {"start_size": 4, "heavy_hitter_size": 1200, "recent_size": 200}),
+                  ("snapkv_lite", {"observation_window": 32, "keep_size": 1200,
+                                   "pooling_kernel": 5})):
+        add(m, kw, "fp32", [P(big, s + 520)], "nan")
+    add("fix_size_l2", {"fix_kv_size": 1400, "keep_ratio": 0.0, "strategy": "keep_low",
+                        "skip_layers": []}, "bf16", [P(big, s + 530)], "nan_no_tail")
+    add("fix_size_l2", {"fix_kv_size": 1400, "keep_ratio": 0.0, "strategy": "keep_low",
+                        "skip_layers": []}, "fp16", [P(big, s + 531)], "nan_no_tail")
+    add("h2o_l2", {"start_size": 4, "heavy_hitter_size": 1200, "recent_size": 200}, "fp16",
+        [P((2, 3, 1500, 80), s + 532)], "nan_D80")
+    add("h2o_l2", {"start_size": 4, "heavy_hitter_size": 1200, "recent_size": 200}, "bf16",
+        [P((2, 3, 1500, 256), s + 533)], "nan_D256")
 
 
 def method_fn(name):
@@ -293,6 +346,7 @@ def run_case(case, positions):
     rec = dict(case)
     layers = make_layers(case)
     rec["input_sha"] = [sha(K) for K, _ in layers]
+    rec["v_input_sha"] = [sha(V) for _, V in layers]
     tin = [(to_torch(K, dt), to_torch(V, dt)) for K, V in layers]
     try:
         out = fn(list(tin), **case["kwargs"])

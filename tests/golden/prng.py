@@ -129,13 +129,122 @@ def gen_keys(seed, shape, dtype, variant="normal"):
         x = (normal_f32(seed, n) * np.float32(scale)).astype(np.float32)
     elif variant == "zero":
         x = np.zeros(n, dtype=np.float32)
+    elif variant == "payload":  # "scaled" keys with NaNs of every sign / payload in every 9th row
+        return _payload_keys(seed, shape, dtype)
     else:
         raise ValueError(variant)
     return to_dtype(x, dtype).reshape(B, H, S, D)
 
 
-def gen_values(seed, shape, dtype):
+# ---- NaN payloads: what torch.gather rewrites and torch.cat copies (tests/test_nan_payload*.py) ----
+BITS = {"bf16": np.uint16, "fp16": np.uint16, "fp32": np.uint32}
+_INF = {"bf16": 0x7F80, "fp16": 0x7C00, "fp32": 0x7F800000}
+_SIGN = {"bf16": 0x8000, "fp16": 0x8000, "fp32": 0x80000000}
+_ONE = {"bf16": 0x3F80, "fp16": 0x3C00, "fp32": 0x3F800000}
+_MANT = {"bf16": 7, "fp16": 10, "fp32": 23}
+
+
+def from_bits(b, dtype):
+    """Bit patterns -> the storage representation (bf16 stays uint16 bits)."""
+    b = np.ascontiguousarray(b, dtype=BITS[dtype])
+    return b if dtype == "bf16" else b.view(np.float16 if dtype == "fp16" else np.float32)
+
+
+def to_bits(a):
+    """The storage representation -> same-width unsigned bit patterns."""
+    a = np.ascontiguousarray(a)
+    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
+
+
+def is_nan_bits(b, dtype):
+    b = np.asarray(b)
+    return (b & (_SIGN[dtype] - 1)) > _INF[dtype]
+
+
+def nan_patterns(dtype):
+    """Every NaN bit pattern of a 16-bit dtype (both signs, payloads ascending, signs alternating);
+    for fp32 the signalling / quiet NaNs of both signs listed in pattern_table()."""
+    if dtype == "fp32":
+        return np.array([0x7F800001, 0xFF800001, 0x7FBFFFFF, 0x7FC00000, 0xFFC00001, 0x7FFFFFFF,
+                         0xFFFFFFFF, 0xFFBFFFFF], dtype=np.uint32)
+    m = np.arange(1, 1 << _MANT[dtype], dtype=np.uint32)
+    pos = m | _INF[dtype]
+    return np.stack([pos, pos | _SIGN[dtype]], axis=1).reshape(-1).astype(np.uint16)
+
+
+def edge_patterns(dtype):
+    """+-0, +-inf, +-largest finite, +-smallest subnormal, 1.0, the smallest normal (fp32: also a
+    mid-range denormal of each sign)."""
+    inf, sg = _INF[dtype], _SIGN[dtype]
+    e = [0, sg, inf, inf | sg, inf - 1, (inf - 1) | sg, 1, 1 | sg, _ONE[dtype], 1 << _MANT[dtype]]
+    if dtype == "fp32":
+        e += [0x00400000, 0x80000123, 0x007FFFFF]
+    return np.array(e, dtype=BITS[dtype])
+
+
+def pattern_table(dtype):
+    """The table T of gen_values(..., "patterns"), as bit patterns: NaN, NaN, edge, NaN, NaN, edge,
+    ... so that (cyclically) every NaN has one NaN and one non-NaN neighbour.  bf16: all 254 NaNs
+    (381 entries); fp16: all 2 046 NaNs (3 069 entries); fp32: 8 NaNs around each of 13 edge
+    values (39 entries).  For the 16-bit types the edge values cycle.  An odd length makes
+    every entry land in both halves of a 32-bit word as the flat element index advances."""
+    nans, edges = nan_patterns(dtype), edge_patterns(dtype)
+    if dtype == "fp32":  # one triple per edge value; the 8 NaNs cycle in steps of 3
+        nans = nans[(3 * np.arange(2 * len(edges))) % len(nans)]
+    assert len(nans) % 2 == 0
+    n3 = len(nans) // 2
+    t = np.empty((n3, 3), dtype=BITS[dtype])
+    t[:, :2] = nans.reshape(n3, 2)
+    t[:, 2] = edges[np.arange(n3) % len(edges)]
+    t = t.reshape(-1)
+    if len(t) % 2 == 0:
+        t = np.concatenate([t, edges[n3 % len(edges):][:1]])
+    assert len(t) % 2 == 1
+    return t
+
+
+def _patterns(shape, dtype):
     B, H, S, D = shape
+    T = pattern_table(dtype)
+    i = (np.arange(S, dtype=np.int64)[:, None] * D + np.arange(D, dtype=np.int64)[None, :])
+    bh = 17 * np.arange(B * H, dtype=np.int64).reshape(B, H, 1, 1)
+    return from_bits(T[(i[None, None] + bh) % len(T)], dtype)
+
+
+def _payload_keys(seed, shape, dtype):
+    """"scaled" keys; row s of every (b, h) with s % 9 == 4 gets a NaN from the pattern table at
+    element 3 (chosen by row: mixed signs and payloads) and, every other such row, a second one at
+    element 6 -- NaNs in odd and even lanes; a few rows of +-inf and +-0 as in "special"."""
+    B, H, S, D = shape
+    K = to_bits(gen_keys(seed, shape, dtype, "scaled")).copy().reshape(B * H, S, D)
+    sel = (splitmix64(seed ^ 0x99, S) % np.uint64(23)).astype(np.int64)
+    inf, sg = _INF[dtype], _SIGN[dtype]
+    K[:, sel == 2, 5] = inf
+    K[:, sel == 3, 0] = inf | sg
+    K[:, sel == 4, :] = 0
+    K[:, sel == 5, :] = sg
+    return inject_payload(from_bits(K.reshape(B, H, S, D), dtype), dtype)
+
+
+def inject_payload(K, dtype):
+    """The NaNs of the "payload" variant written into given keys [B, H, S, D] (a copy)."""
+    B, H, S, D = K.shape
+    out = to_bits(K).copy().reshape(B * H, S, D)
+    nans = nan_patterns(dtype)
+    rows = np.arange(S)[np.arange(S) % 9 == 4]
+    for r in range(B * H):
+        out[r, rows, 3] = nans[(3 * (rows // 9 + 5 * r)) % len(nans)]
+        two = rows[(rows // 9) % 2 == 1]
+        out[r, two, 6] = nans[(3 * (two // 9 + 5 * r) + 1) % len(nans)]
+    return from_bits(out.reshape(B, H, S, D), dtype)
+
+
+def gen_values(seed, shape, dtype, variant="normal"):
+    B, H, S, D = shape
+    if variant == "patterns":  # V[b,h,s,d] = T[(s*D + d + 17*(b*H + h)) % len(T)]
+        return _patterns(shape, dtype)
+    if variant != "normal":
+        raise ValueError(variant)
     return to_dtype(normal_f32(seed ^ 0xABCDEF, B * H * S * D), dtype).reshape(B, H, S, D)
 
 

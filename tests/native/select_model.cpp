@@ -170,6 +170,11 @@ extern "C" uint32_t model_key_f16(uint32_t b, int desc) { return kvc::key_f16(b,
 extern "C" uint32_t model_f32_to_f16(float f) { return kvc::f32_to_f16_rne(f); }
 extern "C" float model_f16_to_f32(uint32_t h) { return kvc::f16_to_f32(h); }
 extern "C" uint32_t model_canon_nan_f16(uint32_t w) { return kvc::canon_nan_f16x2(w); }
+// n words at once (tests/test_nan_payload.py sweeps all 65 536 values of each half)
+extern "C" void model_canon_nan_words(const uint32_t* w, int n, int f16, uint32_t* out) {
+  for (int i = 0; i < n; ++i)
+    out[i] = f16 ? kvc::canon_nan_f16x2(w[i]) : kvc::canon_nan_bf16x2(w[i]);
+}
 
 
 // ---- the select kernel's register heap (RegHeap in csrc/kvc_select_chain.h), 64 lanes simulated
