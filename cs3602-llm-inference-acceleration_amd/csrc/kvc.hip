@@ -176,6 +176,43 @@ static inline size_t tmax_offset(const kvc_plan_info_t& info, int dtype) {
   return off;
 }
 
+// ---- checks shared by the dest and paged plans ----
+// byte span [lo, hi) of a view with three stepped dims (sizes, element strides) of rows of rowb
+// bytes
+struct Span {
+  uintptr_t lo, hi;
+};
+static Span span(const void* base, const int64_t (&size)[3], const int64_t (&st)[3], int es,
+                 int64_t rowb) {
+  int64_t neg = 0, pos = 0;
+  for (int d = 0; d < 3; ++d) {
+    const int64_t ext = (size[d] - 1) * st[d] * es;
+    (ext < 0 ? neg : pos) += ext;
+  }
+  return {(uintptr_t)base + neg, (uintptr_t)base + pos + rowb};
+}
+// some destination range meets some source range (K and V of each)
+static bool ranges_meet(const Span (&dst)[2], const Span (&src)[2]) {
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      if (dst[a].lo < src[b].hi && src[b].lo < dst[a].hi) return true;
+  return false;
+}
+// every stepped stride of a [B, H, n_out, D] destination is a multiple of 16 bytes
+static bool dest_strides_aligned(const kvc_dest_t& d, int64_t B, int64_t H, int64_t n_out, int es) {
+  const int64_t n[3] = {B, H, n_out};
+  for (int i = 0; i < 3; ++i)
+    if (n[i] > 1 && ((d.k_stride[i] * es) % 16 || (d.v_stride[i] * es) % 16)) return false;
+  return true;
+}
+// An in-place copy needs a row map that is strictly increasing with src(t) >= t (gather_passes'
+// ordering proof, kvc_gather_dest.h): sink, zone and tail in that order, none overlapping.
+static bool in_place_row_map_ok(const kvc_layer_t& y) {
+  return !((y.n_select > 0 && y.sink_len > y.zone_start) ||
+           (y.tail_len > 0 && ((int64_t)y.zone_start + y.zone_len > y.tail_start ||
+                               y.sink_len > y.tail_start)));
+}
+
 // kvc_plan_dest / kvc_launch_dest: plan_impl, then the destinations of every layer with output
 // (include/kvc.h, "Caller-provided destinations").  dests == nullptr: plan_impl alone.
 static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_dest_t* dests,
@@ -186,52 +223,31 @@ static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_
   const int es = esize(p->dtype);
   const int64_t rowb = (int64_t)p->head_dim * es;
   const int64_t B = p->batch, H = p->heads;
-  // byte span [lo, hi) of a [B, H, n, D] view
-  const auto span = [&](const void* base, const int64_t* st, int64_t n, uintptr_t* lo,
-                        uintptr_t* hi) {
-    const int64_t size[3] = {B, H, n};
-    int64_t neg = 0, pos = 0;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t ext = (size[d] - 1) * st[d] * es;
-      (ext < 0 ? neg : pos) += ext;
-    }
-    *lo = (uintptr_t)base + neg;
-    *hi = (uintptr_t)base + pos + rowb;
-  };
   for (int l = 0; l < nl; ++l) {
     const kvc_layer_t& y = layers[l];
     const kvc_dest_t& d = dests[l];
     const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
     if (n_out == 0) continue;
     if (d.reserved != 0 || (d.in_place != 0 && d.in_place != 1)) return KVC_E_ARG;
+    if (!dest_strides_aligned(d, B, H, n_out, es)) return KVC_E_ALIGN;
     const int64_t* ks = d.k_stride;
     const int64_t* vs = d.v_stride;
-    if ((B > 1 && ((ks[0] * es) % 16 || (vs[0] * es) % 16)) ||
-        (H > 1 && ((ks[1] * es) % 16 || (vs[1] * es) % 16)) ||
-        (n_out > 1 && ((ks[2] * es) % 16 || (vs[2] * es) % 16)))
-      return KVC_E_ALIGN;
     if (d.in_place) {
       if (y.k_out != y.k || y.v_out != y.v || memcmp(ks, y.k_stride, sizeof(y.k_stride)) ||
           memcmp(vs, y.v_stride, sizeof(y.v_stride)))
         return KVC_E_ARG;
-      // the row map must be strictly increasing with src(t) >= t
-      if ((y.n_select > 0 && y.sink_len > y.zone_start) ||
-          (y.tail_len > 0 && ((int64_t)y.zone_start + y.zone_len > y.tail_start ||
-                              y.sink_len > y.tail_start)))
-        return KVC_E_ARG;
+      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
       // a zero stride (an expanded batch) would be written twice
       if ((B > 1 && (ks[0] == 0 || vs[0] == 0)) || (H > 1 && (ks[1] == 0 || vs[1] == 0)) ||
           (y.seq_len > 1 && (ks[2] == 0 || vs[2] == 0)))
         return KVC_E_ARG;
     } else {
-      uintptr_t slo[2], shi[2], dlo[2], dhi[2];
-      span(y.k, y.k_stride, y.seq_len, &slo[0], &shi[0]);
-      span(y.v, y.v_stride, y.seq_len, &slo[1], &shi[1]);
-      span(y.k_out, ks, n_out, &dlo[0], &dhi[0]);
-      span(y.v_out, vs, n_out, &dlo[1], &dhi[1]);
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
-          if (dlo[a] < shi[b] && slo[b] < dhi[a]) return KVC_E_ARG;
+      const int64_t ssize[3] = {B, H, y.seq_len}, dsize[3] = {B, H, n_out};
+      const Span src[2] = {span(y.k, ssize, y.k_stride, es, rowb),
+                           span(y.v, ssize, y.v_stride, es, rowb)};
+      const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
+                           span(y.v_out, dsize, d.v_stride, es, rowb)};
+      if (ranges_meet(dst, src)) return KVC_E_ARG;
     }
   }
   return KVC_OK;
@@ -249,17 +265,6 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
   const int es = esize(p->dtype);
   const int64_t rowb = (int64_t)p->head_dim * es;
   const int64_t B = p->batch, H = p->heads;
-  // byte span [lo, hi) of a view with three stepped dims
-  const auto span = [&](const void* base, const int64_t (&size)[3], const int64_t (&st)[3],
-                        uintptr_t* lo, uintptr_t* hi) {
-    int64_t neg = 0, pos = 0;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t ext = (size[d] - 1) * st[d] * es;
-      (ext < 0 ? neg : pos) += ext;
-    }
-    *lo = (uintptr_t)base + neg;
-    *hi = (uintptr_t)base + pos + rowb;
-  };
   for (int l = 0; l < nl; ++l) {
     const kvc_layer_t& y = layers[l];
     const kvc_pages_t& g = pages[l];
@@ -277,11 +282,7 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
       return KVC_E_ALIGN;
     if (g.in_place) {
       if (y.k_out != y.k || y.v_out != y.v) return KVC_E_ARG;
-      // the row map must be strictly increasing with src(t) >= t (plan_dest_impl's rule)
-      if ((y.n_select > 0 && y.sink_len > y.zone_start) ||
-          (y.tail_len > 0 && ((int64_t)y.zone_start + y.zone_len > y.tail_start ||
-                              y.sink_len > y.tail_start)))
-        return KVC_E_ARG;
+      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
       // a zero stride would make different logical rows one address
       if ((H > 1 && (y.k_stride[1] == 0 || y.v_stride[1] == 0)) ||
           (P > 1 && y.seq_len > 1 && (y.k_stride[2] == 0 || y.v_stride[2] == 0)) ||
@@ -292,24 +293,14 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
     if (!dests) continue;  // contiguous k_out / v_out
     const kvc_dest_t& d = dests[l];
     if (d.reserved != 0 || d.in_place != 0) return KVC_E_ARG;
-    const int64_t* ks = d.k_stride;
-    const int64_t* vs = d.v_stride;
-    if ((B > 1 && ((ks[0] * es) % 16 || (vs[0] * es) % 16)) ||
-        (H > 1 && ((ks[1] * es) % 16 || (vs[1] * es) % 16)) ||
-        (n_out > 1 && ((ks[2] * es) % 16 || (vs[2] * es) % 16)))
-      return KVC_E_ALIGN;
-    uintptr_t slo[2], shi[2], dlo[2], dhi[2];
+    if (!dest_strides_aligned(d, B, H, n_out, es)) return KVC_E_ALIGN;
     const int64_t psize[3] = {g.num_pages, H, P}, dsize[3] = {B, H, n_out};
     const int64_t kst[3] = {g.k_page_stride, y.k_stride[1], y.k_stride[2]};
     const int64_t vst[3] = {g.v_page_stride, y.v_stride[1], y.v_stride[2]};
-    const int64_t dks[3] = {ks[0], ks[1], ks[2]}, dvs[3] = {vs[0], vs[1], vs[2]};
-    span(y.k, psize, kst, &slo[0], &shi[0]);
-    span(y.v, psize, vst, &slo[1], &shi[1]);
-    span(y.k_out, dsize, dks, &dlo[0], &dhi[0]);
-    span(y.v_out, dsize, dvs, &dlo[1], &dhi[1]);
-    for (int a = 0; a < 2; ++a)
-      for (int b = 0; b < 2; ++b)
-        if (dlo[a] < shi[b] && slo[b] < dhi[a]) return KVC_E_ARG;
+    const Span src[2] = {span(y.k, psize, kst, es, rowb), span(y.v, psize, vst, es, rowb)};
+    const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
+                         span(y.v_out, dsize, d.v_stride, es, rowb)};
+    if (ranges_meet(dst, src)) return KVC_E_ARG;
   }
   return KVC_OK;
 }
@@ -353,14 +344,24 @@ static int with_nc(int nc, F&& f) {
 
 // Keys are read once (non-temporal loads) and outputs written once (non-temporal stores): they
 // would otherwise evict useful lines from the Infinity Cache.
+// (grid: one tile per wave, score_waves(NC) tiles per workgroup)
 template <int DT, int NC>
 static int launch_score(const LayerChunk& T, int nl, int H, int64_t tile_base,
                         int64_t chunk_tiles, char* norms, int64_t nstride, uint32_t* tmax,
                         hipStream_t s) {
-  constexpr int per_wg = score_waves(NC);  // one tile per wave
-  const unsigned grid = (unsigned)((chunk_tiles + per_wg - 1) / per_wg);
-  return launch_k(score_kernel<DT, NC>, dim3(grid), dim3(per_wg * 64), 0, s, T, nl, H,
-                  tile_base, chunk_tiles, norms, nstride, tmax, nstride / kTile);
+  constexpr int per_wg = score_waves(NC);
+  return launch_k(score_kernel<DT, NC>, dim3((unsigned)((chunk_tiles + per_wg - 1) / per_wg)),
+                  dim3(per_wg * 64), 0, s, T, nl, H, tile_base, chunk_tiles, norms, nstride, tmax,
+                  nstride / kTile);
+}
+template <int DT, int NC>
+static int launch_score_paged(const PagesChunk& C, int nl, int H, int64_t tile_base,
+                              int64_t chunk_tiles, char* norms, int64_t nstride, uint32_t* tmax,
+                              uint32_t* status, hipStream_t s) {
+  constexpr int per_wg = score_waves(NC);
+  return launch_k(score_paged_kernel<DT, NC>, dim3((unsigned)((chunk_tiles + per_wg - 1) / per_wg)),
+                  dim3(per_wg * 64), 0, s, C, nl, H, tile_base, chunk_tiles, norms, nstride, tmax,
+                  nstride / kTile, status);
 }
 
 // `work` = max n_out over the chunk's layers; grid = (rows, token blocks)
@@ -381,8 +382,19 @@ static int launch_gather(const LayerChunk& T, int nl, int H, int BH, const int32
                   dim3(kGatherThreads), 0, s, T, H, BH, idx, istride, shared, status, part, 0, nby);
 }
 
-// GATHER of a dest launch: grid = (rows, passes of the longest output that is not in place); an
-// in-place row is one workgroup's
+// Grid of a gather_passes kernel: (rows, passes of the longest output that is not in place); an
+// in-place row (in_place(l) != 0) is one workgroup's
+template <int NC, typename F>
+static dim3 pass_grid(const kvc_layer_t* layers, int nl, int BH, F&& in_place) {
+  int64_t work = 0;  // longest output copied by token blocks
+  for (int l = 0; l < nl; ++l)
+    if (!in_place(l) && layers[l].n_out > work) work = layers[l].n_out;
+  constexpr int rows_per = dest_pass_rows(NC);
+  const int nby = work > 0 ? (int)((work + rows_per - 1) / rows_per) : 1;
+  return dim3((unsigned)(nl * BH), (unsigned)nby);
+}
+
+// GATHER of a dest launch
 template <int DT, int NC>
 static int launch_gather_dest(const LayerChunk& T, const kvc_dest_t* dests, int nl, int H, int BH,
                               const int32_t* idx, int64_t istride, int shared, uint32_t* status,
@@ -390,13 +402,9 @@ static int launch_gather_dest(const LayerChunk& T, const kvc_dest_t* dests, int 
   DestChunk D;
   memset(&D, 0, sizeof(D));
   memcpy(D.d, dests, (size_t)nl * sizeof(kvc_dest_t));
-  int64_t work = 0;  // longest output copied by token blocks
-  for (int l = 0; l < nl; ++l)
-    if (!dests[l].in_place && T.l[l].n_out > work) work = T.l[l].n_out;
-  constexpr int rows_per = dest_pass_rows(NC);
-  const int nby = work > 0 ? (int)((work + rows_per - 1) / rows_per) : 1;
-  return launch_k(gather_dest_kernel<DT, NC>, dim3((unsigned)(nl * BH), (unsigned)nby),
-                  dim3(kGatherThreads), 0, s, T, D, H, BH, idx, istride, shared, status);
+  const dim3 grid = pass_grid<NC>(T.l, nl, BH, [&](int l) { return dests[l].in_place; });
+  return launch_k(gather_dest_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, T, D, H, BH, idx,
+                  istride, shared, status);
 }
 
 // The by-value tables of a paged chunk (<= kPagedLayers layers): layers, page descriptions, and
@@ -419,27 +427,20 @@ static void fill_pages_chunk(PagesChunk* C, const kvc_params_t* p, const kvc_lay
   }
 }
 
-template <int DT, int NC>
-static int launch_score_paged(const PagesChunk& C, int nl, int H, int64_t tile_base,
-                              int64_t chunk_tiles, char* norms, int64_t nstride, uint32_t* tmax,
-                              uint32_t* status, hipStream_t s) {
-  constexpr int per_wg = score_waves(NC);  // one tile per wave
-  const unsigned grid = (unsigned)((chunk_tiles + per_wg - 1) / per_wg);
-  return launch_k(score_paged_kernel<DT, NC>, dim3(grid), dim3(per_wg * 64), 0, s, C, nl, H,
-                  tile_base, chunk_tiles, norms, nstride, tmax, nstride / kTile, status);
-}
-
-// GATHER of a paged launch: grid as launch_gather_dest's (an in-place row is one workgroup's)
+// GATHER of a paged launch
 template <int DT, int NC>
 static int launch_gather_paged(const PagesChunk& C, int nl, int H, int BH, const int32_t* idx,
                                int64_t istride, int shared, uint32_t* status, hipStream_t s) {
-  int64_t work = 0;  // longest output copied by token blocks
-  for (int l = 0; l < nl; ++l)
-    if (!C.p[l].in_place && C.l[l].n_out > work) work = C.l[l].n_out;
-  constexpr int rows_per = dest_pass_rows(NC);
-  const int nby = work > 0 ? (int)((work + rows_per - 1) / rows_per) : 1;
-  return launch_k(gather_paged_kernel<DT, NC>, dim3((unsigned)(nl * BH), (unsigned)nby),
-                  dim3(kGatherThreads), 0, s, C, H, BH, idx, istride, shared, status);
+  const dim3 grid = pass_grid<NC>(C.l, nl, BH, [&](int l) { return C.p[l].in_place; });
+  return launch_k(gather_paged_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, C, H, BH, idx,
+                  istride, shared, status);
+}
+
+// The 512-thread selection kernels (zones up to kSmallZone) over n_cap positions: the candidate
+// capacity that fits the LDS budget (*cap) and the dynamic LDS bytes; wave segment kWaveSegSmall
+static size_t small_sel_lds(int n_cap, int key_size, int* cap) {
+  *cap = sel_cap(n_cap, key_size, kSmallBudget);
+  return sel_bytes(n_cap, key_size, *cap);
 }
 
 // SELECT over the rows of a chunk (BH rows per layer, workspace row ly->row0 + blockIdx % BH):
@@ -470,11 +471,11 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
   const auto go = [&](auto stable) {
     constexpr bool ST = decltype(stable)::value;
     if (n_cap <= kSmallZone) {
-      const int cap = sel_cap(n_cap, ks, kSmallBudget);
+      int cap;
+      const size_t lds = small_sel_lds(n_cap, ks, &cap);
       return launch_k(select_kernel<KC, kSelThreadsSmall, HH, ST>, rows_grid,
-                      dim3(kSelThreadsSmall), sel_bytes(n_cap, ks, cap), s, T, BH, dt, order, algo,
-                      norms, nstride, idx, istride, kWaveSegSmall, n_cap, cap, stamps, status,
-                      tmax);
+                      dim3(kSelThreadsSmall), lds, s, T, BH, dt, order, algo, norms, nstride, idx,
+                      istride, kWaveSegSmall, n_cap, cap, stamps, status, tmax);
     }
     return launch_k(select_kernel<KC, kSelThreads, HH, ST>, rows_grid, dim3(kSelThreads), 0, s, T,
                     BH, dt, order, algo, norms, nstride, idx, istride, kWaveSeg, n_cap, 0, stamps,
@@ -550,11 +551,11 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
       const auto go = [&](auto stable) {
         constexpr bool ST = decltype(stable)::value;
         if (n_cap <= kSmallZone) {
-          const int cap = sel_cap(n_cap, ks, kSmallBudget);
+          int cap;
+          const size_t lds = small_sel_lds(n_cap, ks, &cap);
           return launch_k(select_gather_kernel<KC, kSelThreadsSmall, NC, ST>, rows_grid,
-                          dim3(kSelThreadsSmall), sel_bytes(n_cap, ks, cap), s, T, H, BH, DT,
-                          p->order, p->algo, norms, nstride, kWaveSegSmall, n_cap, cap, status, 0,
-                          tmax);
+                          dim3(kSelThreadsSmall), lds, s, T, H, BH, DT, p->order, p->algo, norms,
+                          nstride, kWaveSegSmall, n_cap, cap, status, 0, tmax);
         }
         // fewer rows than CUs (e.g. 4 layers per GPU of an 8-way layer split): one row per CU
         // and idle CUs -- the sink / tail rows get copy-only workgroups of their own
@@ -623,9 +624,8 @@ static int debug_select_impl(const kvc_params_t* p, const kvc_layer_t* layers, i
   return with_dtype(p->dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
-    const int ks = (int)sizeof(typename DTypeTraits<KC>::key_t);
-    const int cap = sel_cap(zone_cap, ks, kSmallBudget);
-    const size_t lds = sel_bytes(zone_cap, ks, cap);
+    int cap;
+    const size_t lds = small_sel_lds(zone_cap, (int)sizeof(typename DTypeTraits<KC>::key_t), &cap);
     if (p->phases == KVC_PHASE_SELECT)
       return launch_k(select_kernel<KC, kSelThreadsSmall>, grid, dim3(kSelThreadsSmall), lds, s,
                       T, BH, DT, p->order, p->algo, norms, info.norm_row_stride, idx,

@@ -1,6 +1,7 @@
 // kvc_paged.h -- paged K/V sources (kvc_launch_paged): SCORE and GATHER of layers whose rows live
 // in a page pool addressed through a per-sequence block table (include/kvc.h, "Paged caches").
-// SELECT reads the workspace only and runs the kernels of kvc_select.h unchanged.
+// GATHER is the pass schedule of kvc_gather_dest.h over the block-table policy below.  SELECT
+// reads the workspace only and runs the kernels of kvc_select.h unchanged.
 #pragma once
 
 #include "kvc_gather_dest.h"
@@ -44,8 +45,13 @@ struct PageRow {
 // through the block table.  Same tile structure (one wave = 64 consecutive zone tokens of one
 // (layer, b, h) row), LDS slab, FMA order, non-temporal loads, norm stores and snapkv tile
 // maxima; a tile may start anywhere in a page and span many pages or a fraction of one.  Each lane
-// stages CP (token, 16-B chunk) units per phase, of CP / gcd distinct tokens; the page id of a unit's
-// token is looked up ONCE, before the phases, and kept as the unit's row pointer.
+// stages CP (token, 16-B chunk) units per phase, of CP / gcd distinct tokens; the page id of a
+// unit's token is looked up ONCE, before the phases, and kept as the unit's row pointer.
+// The tile is a COPY of score_tile from `float acc[8]` on, deliberately: as one body over a
+// row-source policy (tried with valid/ptr and with load methods, by value, by reference and over a
+// local pointer array) score_paged_kernel<*, 20> takes 150 VGPRs instead of 130-132 and the
+// CP = 10 instances 36-77 more instructions, and a reordered score_kernel is all the dense side
+// gains.  A fix to one tile is a fix to both.
 // ---------------------------------------------------------------------------------------------
 template <int DT, int NC>
 __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kvc_pages_t* pg,
@@ -143,165 +149,77 @@ __global__ void __launch_bounds__(score_waves(NC) * 64)
   constexpr int ROWB = score_rowb(CP);
   constexpr int kScoreWaves = score_waves(NC);
   __shared__ __attribute__((aligned(16))) char lds[kScoreWaves][kTile * ROWB];
-  const kvc_layer_t* L = T.l;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t stride = (int64_t)gridDim.x * kScoreWaves;
   for (int64_t gl = (int64_t)blockIdx.x * kScoreWaves + wid; gl < chunk_tiles; gl += stride) {
-    const int64_t g = tile_base + gl;  // global tile index (kvc_plan's tile0 numbering)
-    int lo = 0, hi = nl - 1;  // largest layer with tile0 <= g
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (L[mid].tile0 <= g)
-        lo = mid;
-      else
-        hi = mid - 1;
-    }
-    const kvc_layer_t* ly = L + lo;
-    const int tpr = (ly->zone_len + kTile - 1) / kTile;
-    const int local = (int)(g - ly->tile0);
-    const int row = local / tpr;
-    score_paged_tile<DT, NC>(ly, T.p + lo, row, local - row * tpr, H, lds[wid], norms,
+    const TileAt at = locate_tile(T.l, nl, tile_base + gl);
+    score_paged_tile<DT, NC>(T.l + at.layer, T.p + at.layer, at.row, at.tile, H, lds[wid], norms,
                              norm_stride, tmax, tmax_stride, status);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// GATHER of paged sources: the rows gather_dest_kernel copies, read through the block table, into
+// GATHER of paged sources: gather_passes (kvc_gather_dest.h) reading through the block table, into
 //   * a dense destination (kvc_pages_t.in_place == 0): b * os0 + h * os1 + t * os2 of T.d -- the
-//     layer's kvc_dest_t, or the strides of a contiguous k_out / v_out; block (row, by) copies
-//     one pass of dest_pass_rows(NC) output rows, no ordering constraint;
+//     layer's kvc_dest_t, or the strides of a contiguous k_out / v_out;
 //   * the pool itself (in_place == 1): output row t goes to the slot of LOGICAL row t through the
-//     same table.  gather_dest_kernel's schedule: ONE workgroup per (layer, b, h) row -- block
-//     (row, 0) -- ascending passes of consecutive output rows, and in every pass all loads have
-//     returned in every wave (s_waitcnt vmcnt(0), then the barrier) before any store.
+//     same table, on the in-place schedule.
 //
-// Why that is still a correct memmove.  The proof in kvc_gather_dest.h speaks about ROWS, not
-// addresses: the row map is strictly increasing with src(t) >= t (kvc_plan_paged applies
-// kvc_plan_dest's segment-order rule; ascending indices), so output row t overwrites only a
-// logical row that is the source of output rows <= t; a pass's stores follow all of its loads; the
-// sources of pass p+1 are logical rows above every destination of passes <= p.  What the proof
-// needs from memory is only that DIFFERENT logical rows of one (b, h) sequence are different
-// bytes.  With a block table, logical row s is (page table[s >> lg], slot s & (P-1)): distinct
-// page ids within a table row (the caller's promise) and non-zero, non-overlapping strides make
-// s -> address injective, whatever order the pages have in the pool -- a shuffled table permutes
-// addresses, not rows.  Different (b, h) rows, K and V, and layers share no written page (the
-// promise), so workgroups do not meet.  The table is only read.  Sink rows have src == dst and
-// are not touched, so pages holding only sink rows may be shared between sequences.
+// Why that is still a correct memmove: what gather_passes' proof needs from memory is that
+// DIFFERENT logical rows of one (b, h) sequence are different bytes (kvc_plan_paged applies the
+// same row-map rule).  With a block table, logical row s is (page table[s >> lg], slot
+// s & (P-1)): distinct page ids within a table row (the caller's promise) and non-zero,
+// non-overlapping strides make s -> address injective, whatever order the pages have in the pool
+// -- a shuffled table permutes addresses, not rows.  Different (b, h) rows, K and V, and layers
+// share no written page (the promise), so workgroups do not meet.  The table is only read.  Sink
+// rows have src == dst and are not touched, so pages holding only sink rows may be shared between
+// sequences.
 // An in-place store through a page id outside [0, num_pages) is DROPPED (loads are clamped).
 // ---------------------------------------------------------------------------------------------
+// Rows of one (b, h) sequence of a paged K and V.
+struct PagedRows {
+  PageRow pr;
+  char* kb;
+  char* vb;
+  int64_t kss, vss, kps, vps;
+  // bad page ids and indices fold into one flag: one atomicOr per thread
+  static constexpr bool kFoldStatus = true;
+  __device__ __forceinline__ PagedRows(int esz, const kvc_layer_t* ly, const kvc_pages_t* pg,
+                                       int b, int h)
+      : pr(pg, b),
+        kb((char*)ly->k + (int64_t)h * ly->k_stride[1] * esz),
+        vb((char*)ly->v + (int64_t)h * ly->v_stride[1] * esz),
+        kss(ly->k_stride[2] * esz),
+        vss(ly->v_stride[2] * esz),
+        kps(pg->k_page_stride * esz),
+        vps(pg->v_page_stride * esz) {}
+  // addresses of logical row s through the clamped page id; false: the id was out of range
+  __device__ __forceinline__ bool locate(int s, char** k, char** v) const {
+    bool ok;
+    const int64_t id = pr.page(s, &ok);
+    const int slot = s & pr.mask;
+    *k = kb + id * kps + slot * kss;
+    *v = vb + id * vps + slot * vss;
+    return ok;
+  }
+};
+
 template <int DT, int NC>
 __global__ void __launch_bounds__(kGatherThreads)
     gather_paged_kernel(const PagesChunk T, int H, int BH, const int32_t* __restrict__ gidx,
                         int64_t idx_stride, int shared, uint32_t* status) {
-  constexpr int ESZ = DTypeTraits<DT>::esz;
-  constexpr int ROWS = dest_pass_rows(NC);
   const int li = (int)blockIdx.x / BH;
   const kvc_layer_t* ly = T.l + li;
   const kvc_pages_t* pg = T.p + li;
   const kvc_dest_t* de = T.d + li;
   const int r = (int)blockIdx.x - li * BH;
-  const int n_out = ly->n_out;
-  const bool inplace = pg->in_place != 0;
-  const int sink = ly->sink_len, nsel = ly->n_select;
-  int t_begin, t_end;
-  if (inplace) {
-    if (blockIdx.y != 0) return;
-    t_begin = sink;
-    t_end = n_out;
-  } else {
-    t_begin = (int)blockIdx.y * ROWS;
-    t_end = min(n_out, t_begin + ROWS);
-  }
-  if (t_begin >= t_end) return;
   const int b = r / H, h = r - (r / H) * H;
-  const PageRow pr(pg, b);
-  const char* kb = static_cast<const char*>(ly->k) + (int64_t)h * ly->k_stride[1] * ESZ;
-  const char* vb = static_cast<const char*>(ly->v) + (int64_t)h * ly->v_stride[1] * ESZ;
-  const int64_t kss = ly->k_stride[2] * ESZ, vss = ly->v_stride[2] * ESZ;
-  const int64_t kps = pg->k_page_stride * ESZ, vps = pg->v_page_stride * ESZ;
-  // dense destination rows (unused in place)
-  char* ko = static_cast<char*>(ly->k_out) +
-             ((int64_t)b * de->k_stride[0] + (int64_t)h * de->k_stride[1]) * ESZ;
-  char* vo = static_cast<char*>(ly->v_out) +
-             ((int64_t)b * de->v_stride[0] + (int64_t)h * de->v_stride[1]) * ESZ;
-  const int64_t kos = de->k_stride[2] * ESZ, vos = de->v_stride[2] * ESZ;
-  // index row of (layer, b, h); KVC_FLAG_SHARED_INDEX: (layer, b)'s row serves every head
-  const int32_t* irow = gidx + (int64_t)((ly->row0 + r) / (shared ? H : 1)) * idx_stride;
-  const int zone_len = ly->zone_len, zone_start = ly->zone_start, tail_start = ly->tail_start;
-  bool bad = false;
-  for (int t0 = t_begin; t0 < t_end; t0 += ROWS) {  // ascending passes
-    const int nu = min(ROWS, t_end - t0) * NC;
-    uint4 xk[kDestIters], xv[kDestIters];
-    bool gat[kDestIters];
-    int zi[kDestIters];
-#pragma unroll
-    for (int i = 0; i < kDestIters; ++i) {
-      const int u = threadIdx.x + i * kGatherThreads;
-      const int t = t0 + u / NC;
-      gat[i] = u < nu && t >= sink && t < sink + nsel;
-      zi[i] = gat[i] ? irow[t - sink] : 0;
-    }
-#pragma unroll
-    for (int i = 0; i < kDestIters; ++i) {
-      const int u = threadIdx.x + i * kGatherThreads;
-      if (u < nu) {
-        const int t = t0 + u / NC, c = u - (u / NC) * NC;
-        int src;
-        if (t < sink) {
-          src = t;
-        } else if (gat[i]) {
-          bad |= zi[i] < 0 || zi[i] >= zone_len;  // never read outside the zone: clamp
-          src = zone_start + min(max(zi[i], 0), zone_len - 1);
-        } else {
-          src = tail_start + (t - sink - nsel);
-        }
-        bool ok;
-        const int64_t id = pr.page(src, &ok);  // one lookup per (lane, row): K and V share it
-        bad |= !ok;
-        const int slot = src & pr.mask;
-        xk[i] = *reinterpret_cast<const uint4*>(kb + id * kps + slot * kss + c * 16);
-        xv[i] = *reinterpret_cast<const uint4*>(vb + id * vps + slot * vss + c * 16);
-      }
-    }
-    if (inplace) {  // uniform over the workgroup
-      // every load of this pass has returned in this wave, then in all waves, before any store
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < kDestIters; ++i) {
-      const int u = threadIdx.x + i * kGatherThreads;
-      if (u < nu) {
-        const int t = t0 + u / NC, c = u - (u / NC) * NC;
-        uint4 a = xk[i], q = xv[i];
-        if (gat[i]) {  // torch.gather's NaN rewrite (gathered segment only)
-          a = canon_nan_dt<DT>(a);
-          q = canon_nan_dt<DT>(q);
-        }
-        char* kd;
-        char* vd;
-        bool ok = true;
-        if (inplace) {  // the slot of logical row t
-          const int64_t id = pr.page(t, &ok);
-          bad |= !ok;
-          const int slot = t & pr.mask;
-          kd = const_cast<char*>(kb) + id * kps + slot * kss;
-          vd = const_cast<char*>(vb) + id * vps + slot * vss;
-        } else {
-          kd = ko + t * kos;
-          vd = vo + t * vos;
-        }
-        if (ok) {  // a bad page id: the store is dropped, not clamped
-          typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-          __builtin_nontemporal_store(u32x4{a.x, a.y, a.z, a.w},
-                                      reinterpret_cast<u32x4*>(kd + c * 16));
-          __builtin_nontemporal_store(u32x4{q.x, q.y, q.z, q.w},
-                                      reinterpret_cast<u32x4*>(vd + c * 16));
-        }
-      }
-    }
-  }
-  if (bad && status) atomicOr(status, (uint32_t)KVC_DEV_INDEX_RANGE);
+  const bool inplace = pg->in_place != 0;
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  const PagedRows src(ESZ, ly, pg, b, h);
+  const DenseRows dense(ESZ, ly->k_out, ly->v_out, de->k_stride, de->v_stride, b, h);
+  const EitherRows<PagedRows, DenseRows> dst = {inplace, src, dense};
+  gather_passes<DT, NC>(ly, r, H, inplace, src, dst, gidx, idx_stride, shared, status);
 }
 
 }  // namespace kvc

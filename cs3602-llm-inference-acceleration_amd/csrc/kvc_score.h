@@ -136,6 +136,26 @@ __device__ __forceinline__ void score_tile(const kvc_layer_t* ly, int row, int t
   }
 }
 
+// Global tile g (kvc_plan's tile0 numbering) of a chunk of nl layers: its layer, the layer's
+// (b, h) row and the tile within the row.
+struct TileAt {
+  int layer, row, tile;
+};
+__device__ __forceinline__ TileAt locate_tile(const kvc_layer_t* L, int nl, int64_t g) {
+  int lo = 0, hi = nl - 1;  // largest layer with tile0 <= g
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (L[mid].tile0 <= g)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const int tpr = (L[lo].zone_len + kTile - 1) / kTile;
+  const int local = (int)(g - L[lo].tile0);
+  const int row = local / tpr;
+  return {lo, row, local - row * tpr};
+}
+
 template <int DT, int NC>
 __global__ void __launch_bounds__(score_waves(NC) * 64)
     score_kernel(const LayerChunk T, int nl, int H, int64_t tile_base, int64_t chunk_tiles,
@@ -150,20 +170,8 @@ __global__ void __launch_bounds__(score_waves(NC) * 64)
   // one tile per wave (default grid); a smaller grid makes the waves stride over the tiles
   const int64_t stride = (int64_t)gridDim.x * kScoreWaves;
   for (int64_t gl = (int64_t)blockIdx.x * kScoreWaves + wid; gl < chunk_tiles; gl += stride) {
-    const int64_t g = tile_base + gl;  // global tile index (kvc_plan's tile0 numbering)
-    int lo = 0, hi = nl - 1;  // largest layer with tile0 <= g
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (L[mid].tile0 <= g)
-        lo = mid;
-      else
-        hi = mid - 1;
-    }
-    const kvc_layer_t* ly = L + lo;
-    const int tpr = (ly->zone_len + kTile - 1) / kTile;
-    const int local = (int)(g - ly->tile0);
-    const int row = local / tpr;
-    score_tile<DT, NC>(ly, row, local - row * tpr, H, lds[wid], norms, norm_stride, tmax,
+    const TileAt at = locate_tile(L, nl, tile_base + gl);
+    score_tile<DT, NC>(L + at.layer, at.row, at.tile, H, lds[wid], norms, norm_stride, tmax,
                        tmax_stride);
   }
 }

@@ -1,4 +1,5 @@
-"""The ordering argument of in-place compaction (csrc/kvc_gather_dest.h), in numpy, no engine.
+"""The ordering argument of in-place compaction (gather_passes, csrc/kvc_gather_dest.h: the one
+pass schedule of the dense and the paged copy kernel), in numpy, no engine.
 
 For every in-place case of tests/dest_cases.py the row map src(t) of each changed layer is read
 off the oracle's position-tagged V output.  (a) Copying the output rows onto the input in

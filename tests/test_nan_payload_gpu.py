@@ -4,8 +4,9 @@ The reference builds the kept zone with torch.gather, which on the CPU turns eve
 0xFFFF and sets bit 9 of every fp16 NaN, and the rest of an output with torch.cat, which copies
 (oracle.gather; the rule itself is held against torch in tests/test_nan_payload.py).  The engine
 restates that in canon_nan_dt (csrc/kvc_device_util.h), called by gather_block / gather_row
-(csrc/kvc_gather.h), gather_dest_kernel (csrc/kvc_gather_dest.h) and gather_paged_kernel
-(csrc/kvc_paged.h).  Here each of them copies values that run through every NaN pattern of the
+(csrc/kvc_gather.h) and by gather_passes (csrc/kvc_gather_dest.h), the pass body of
+gather_dest_kernel and of gather_paged_kernel (csrc/kvc_paged.h).  Here each of the four kernels'
+paths copies values that run through every NaN pattern of the
 dtype in both halves of a 32-bit word, beside NaN and non-NaN halves (prng "patterns"), and keys
 with non-canonical NaNs of both signs (prng "payload"); every comparison is of raw bytes against
 the CPU oracle, and the device status word stays 0.

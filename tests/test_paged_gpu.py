@@ -341,6 +341,78 @@ def test_c_abi_chunks_shared_index_and_wide_table():
         pls[li].assert_pools(snaps[li], ("shared index", li))
 
 
+IDENTITY_CASES = [("bf16", 80, PT.NORM), ("bf16", 32, PT.NORM), ("fp32", 128, PT.NORM),
+                  ("fp16", 128, PT.SNAPKV)]
+
+
+@pytest.mark.parametrize("dt, D, score_mode", IDENTITY_CASES,
+                         ids=[f"{dt}-D{D}" + ("-snapkv" if m == PT.SNAPKV else "")
+                              for dt, D, m in IDENTITY_CASES])
+def test_identity_table_equals_dense(dt, D, score_mode):
+    """The paged kernels differ from the dense ones in address arithmetic only: SCORE + SELECT +
+    GATHER of one dense [1, H, S, D] K / V, and the same call through kvc_launch_paged over the
+    SAME memory with the identity block table (page i = rows [iP, (i+1)P), page stride
+    P * k_stride[2]), leave byte-identical norms, tile maxima (snapkv), indices and outputs.
+    Zone [5, 135): three tiles, the last of 2 tokens, from the middle of page 0 over nine pages."""
+    H, S, P = 2, 200, 16
+    s = PT.spec(S, zone_start=5, zone_len=130, n_select=40, sink=3, tail_start=190, tail_len=10,
+                score_mode=score_mode, pool=5 if score_mode == PT.SNAPKV else 0)
+    order, algo = (PT.DESC, PT.TOPK) if score_mode == PT.SNAPKV else (PT.ASC, PT.SORT)
+    tdt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[dt]
+    esz = 4 if dt == "fp32" else 2
+    # the last page's slots reach 8 rows past S: backed, so that nothing else lives there
+    kv = []
+    for gen in (lambda: prng.gen_keys(48000 + D, (1, H, S, D), dt, "normal"),
+                lambda: prng.gen_values(48000 + D, (1, H, S, D), dt)):
+        flat = torch.zeros(H * S * D + P * D, dtype=tdt, device=DEV)
+        flat[:H * S * D] = to_dev(gen(), DEV).reshape(-1)
+        kv.append(flat[:H * S * D].view(1, H, S, D))
+    k, v = kv
+    n_pages = (S + P - 1) // P
+    block_table = torch.arange(n_pages, dtype=torch.int32, device=DEV).view(1, n_pages)
+    stream = torch.cuda.current_stream().cuda_stream
+    runs = []
+    for paged in (False, True):
+        outs = tuple(torch.zeros((1, H, PT.n_out(s), D), dtype=tdt, device=DEV) for _ in range(2))
+        table = np.zeros(1, dtype=N.LAYER_DTYPE)
+        t = table[0]
+        t["k"], t["v"], t["k_out"], t["v_out"] = (x.data_ptr() for x in (k, v) + outs)
+        t["k_stride"] = t["v_stride"] = (0 if paged else H * S * D, S * D, D)
+        t["seq_len"], t["zone_start"], t["zone_len"] = S, s["zone_start"], s["zone_len"]
+        t["n_select"], t["sink_len"] = s["n_select"], s["sink"]
+        t["tail_start"], t["tail_len"] = s["tail_start"], s["tail_len"]
+        t["score_mode"], t["pool_kernel"] = s["score_mode"], s["pool"]
+        pages = None
+        if paged:
+            pages = np.zeros(1, dtype=N.PAGES_DTYPE)
+            pages[0] = (block_table.data_ptr(), n_pages, P * D, P * D, P, n_pages, 0, 0)
+        status = torch.zeros(1, dtype=torch.int32, device=DEV)
+        # SELECT and GATHER as two kernels in the dense run too: the index region is written
+        p = _params(1, H, status, order, algo, head_dim=D, flags=N.FLAG_SPLIT_SELECT_GATHER,
+                    dtype={"bf16": N.KVC_BF16, "fp16": N.KVC_F16, "fp32": N.KVC_F32}[dt])
+        rc, info = N.plan_paged(p, table, pages, None)
+        assert rc == 0, (paged, rc)
+        ws = _workspace(info)
+        assert N.launch_paged(p, table, pages, None, ws.data_ptr(), int(info.workspace_bytes),
+                              stream) == 0, paged
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0, paged
+        rows, ns, istr = int(info.rows), int(info.norm_row_stride), int(info.index_row_stride)
+        w = ws.cpu().numpy()
+        norms = w[info.norm_offset:info.norm_offset + rows * ns * esz].reshape(rows, ns * esz)
+        index = w[info.index_offset:info.index_offset + rows * istr * 4]
+        toff = (info.index_offset + rows * istr * 4 + 255) // 256 * 256  # csrc/kvc.hip tmax_offset
+        tmax = w[toff:toff + rows * (ns // 64) * 4]
+        runs.append(dict(norms=norms[:, :s["zone_len"] * esz].copy(), index=index.copy(),
+                         tmax=tmax.copy(), k=_bytes(to_np(outs[0])), v=_bytes(to_np(outs[1])),
+                         layout=(rows, ns, istr, int(info.workspace_bytes))))
+    dense, paged = runs
+    assert dense["layout"] == paged["layout"]
+    assert dense["index"].view(np.int32).reshape(H, -1)[:, :s["n_select"]].min() >= 0
+    for name in ("norms", "index", "k", "v") + (("tmax",) if score_mode == PT.SNAPKV else ()):
+        assert dense[name].size and np.array_equal(dense[name], paged[name]), name
+
+
 @pytest.mark.parametrize("mode", ["copy", "inplace", "select"])
 def test_bad_page_id_is_clamped_for_loads_and_dropped_for_stores(mode):
     """7: N pages allocated, num_pages = N - 4 declared, the table's entry of logical page 1 is

@@ -1,5 +1,6 @@
-"""The ordering argument of in-place compaction through a block table (csrc/kvc_paged.h), in
-numpy, no engine.
+"""The ordering argument of in-place compaction through a block table (the schedule is
+gather_passes, csrc/kvc_gather_dest.h; the table's address arithmetic and why distinct logical
+rows are distinct bytes, csrc/kvc_paged.h), in numpy, no engine.
 
 A pool [N, H, P] of unique ids stands for K (or V); every batch row owns ceil(S / P) pages of a
 seeded permutation and 7 pages stay spare.  For every in-place case of tests/dest_cases.py the row
