@@ -1,10 +1,11 @@
 """Page pools for the paged-cache GPU tests (tests/test_paged_gpu.py, tests/test_paged_graph.py).
 
 A pool has 7 spare pages, is poison-filled and is addressed through a seeded permutation of page
-ids; each batch row gets its own pages.  K pools are stored [N, H, P, D] and V pools
-[N, P, H, D], so their stride triples differ.  Both are handed to the engine as [N, H, P, D]
-views.  Checks compare the WHOLE backing buffer with a snapshot that has the expected rows written
-in through the table: the result and every byte that must not change in one comparison.
+ids; each batch row gets its own pages.  By default K pools are stored [N, H, P, D] and V pools
+[N, P, H, D], so their stride triples differ (Layer's k_storage / v_storage choose otherwise).
+Both are handed to the engine as [N, H, P, D] views.  Checks compare the WHOLE backing buffer with
+a snapshot that has the expected rows written in through the table: the result and every byte
+that must not change in one comparison.
 """
 import numpy as np
 import torch
@@ -56,7 +57,8 @@ def write_rows(view, table, rows, first=0):
 class Layer:
     """One paged layer: K / V backings and views, the device block table, and the PagedKV."""
 
-    def __init__(self, k_np, v_np, P, seed, table=None, n_pages=None, table_cols=None):
+    def __init__(self, k_np, v_np, P, seed, table=None, n_pages=None, table_cols=None,
+                 k_storage="nhpd", v_storage="nphd"):
         from kvcompress import PagedKV
         k, v = to_dev(k_np, DEV), to_dev(v_np, DEV)
         B, H, S, D = k.shape
@@ -67,10 +69,11 @@ class Layer:
         full = np.full((B, cols), -1, dtype=np.int32)  # entries past the sequence are never read
         full[:, :table.shape[1]] = table
         self.table = torch.from_numpy(full).to(DEV)
-        self.kb = new_backing(n_pages, H, P, D, k.dtype, "nhpd")
-        self.vb = new_backing(n_pages, H, P, D, k.dtype, "nphd")
-        self.k, self.v = pool_view(self.kb, "nhpd"), pool_view(self.vb, "nphd")
-        assert self.k.stride() != self.v.stride() or H == 1 or P == 1
+        self.k_storage, self.v_storage = k_storage, v_storage
+        self.kb = new_backing(n_pages, H, P, D, k.dtype, k_storage)
+        self.vb = new_backing(n_pages, H, P, D, k.dtype, v_storage)
+        self.k, self.v = pool_view(self.kb, k_storage), pool_view(self.vb, v_storage)
+        assert (self.k.stride() != self.v.stride()) == (k_storage != v_storage) or H == 1 or P == 1
         write_rows(self.k, table, k)
         write_rows(self.v, table, v)
         self.paged = PagedKV(self.k, self.v, self.table, S)
@@ -80,7 +83,8 @@ class Layer:
 
     def expect(self, snap, k_rows, v_rows, first=0):
         """Write the expected rows (numpy, rows [first, ...)) into a snapshot through the table."""
-        for back, storage, rows in ((snap[0], "nhpd", k_rows), (snap[1], "nphd", v_rows)):
+        for back, storage, rows in ((snap[0], self.k_storage, k_rows),
+                                    (snap[1], self.v_storage, v_rows)):
             write_rows(pool_view(back, storage), self.table_np, to_dev(rows, DEV), first)
 
     def assert_pools(self, snap, ctx):
