@@ -40,6 +40,7 @@
 #include "kvc_attn.h"           // attn_accumulate / head-sum kernels
 #include "kvc_gather_dest.h"    // gather_dest_kernel (kvc_launch_dest)
 #include "kvc_paged.h"          // score_paged_kernel, gather_paged_kernel (kvc_launch_paged)
+#include "kvc_ragged.h"         // the per-sequence-record kernels (kvc_launch_ragged)
 
 namespace kvc {
 
@@ -256,6 +257,35 @@ static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_
 // kvc_plan_paged / kvc_launch_paged: plan_impl, then the page description (and the dense
 // destination, if any) of every layer with output (include/kvc.h, "Paged caches").
 // pages == nullptr: plan_dest_impl.
+// The page description of one layer with output, and what compaction in place asks of it.
+// row_map: apply the in-place row-map rule to y's segments (a ragged layer's rule is checked per
+// record, and y holds their envelope).
+static int paged_layer_check(const kvc_params_t* p, const kvc_layer_t& y, const kvc_pages_t& g,
+                             bool row_map) {
+  const int es = esize(p->dtype);
+  const int64_t H = p->heads;
+  if (!g.block_table || ((uintptr_t)g.block_table & 3u) || g.reserved != 0 ||
+      (g.in_place != 0 && g.in_place != 1) || g.num_pages < 1 || g.page_size < 1 ||
+      g.page_size > 65536 || (g.page_size & (g.page_size - 1)))
+    return KVC_E_ARG;
+  const int64_t P = g.page_size;
+  if (g.table_stride < ((int64_t)y.seq_len + P - 1) / P) return KVC_E_ARG;
+  if (y.k_stride[0] != 0 || y.v_stride[0] != 0) return KVC_E_ARG;  // the table is the batch dim
+  // (plan_impl has checked the head and slot strides against heads > 1 / seq_len > 1)
+  if (g.num_pages > 1 && ((g.k_page_stride * es) % 16 || (g.v_page_stride * es) % 16))
+    return KVC_E_ALIGN;
+  if (g.in_place) {
+    if (y.k_out != y.k || y.v_out != y.v) return KVC_E_ARG;
+    if (row_map && !in_place_row_map_ok(y)) return KVC_E_ARG;
+    // a zero stride would make different logical rows one address
+    if ((H > 1 && (y.k_stride[1] == 0 || y.v_stride[1] == 0)) ||
+        (P > 1 && y.seq_len > 1 && (y.k_stride[2] == 0 || y.v_stride[2] == 0)) ||
+        (g.num_pages > 1 && (g.k_page_stride == 0 || g.v_page_stride == 0)))
+      return KVC_E_ARG;
+  }
+  return KVC_OK;
+}
+
 static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
                            const kvc_dest_t* dests, int nl, kvc_plan_info_t* info, bool fill) {
   if (!pages) return plan_dest_impl(p, layers, dests, nl, info, fill);
@@ -270,26 +300,10 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
     const kvc_pages_t& g = pages[l];
     const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
     if (n_out == 0) continue;
-    if (!g.block_table || ((uintptr_t)g.block_table & 3u) || g.reserved != 0 ||
-        (g.in_place != 0 && g.in_place != 1) || g.num_pages < 1 || g.page_size < 1 ||
-        g.page_size > 65536 || (g.page_size & (g.page_size - 1)))
-      return KVC_E_ARG;
+    rc = paged_layer_check(p, y, g, true);
+    if (rc != KVC_OK) return rc;
+    if (g.in_place) continue;
     const int64_t P = g.page_size;
-    if (g.table_stride < ((int64_t)y.seq_len + P - 1) / P) return KVC_E_ARG;
-    if (y.k_stride[0] != 0 || y.v_stride[0] != 0) return KVC_E_ARG;  // the table is the batch dim
-    // (plan_impl has checked the head and slot strides against heads > 1 / seq_len > 1)
-    if (g.num_pages > 1 && ((g.k_page_stride * es) % 16 || (g.v_page_stride * es) % 16))
-      return KVC_E_ALIGN;
-    if (g.in_place) {
-      if (y.k_out != y.k || y.v_out != y.v) return KVC_E_ARG;
-      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
-      // a zero stride would make different logical rows one address
-      if ((H > 1 && (y.k_stride[1] == 0 || y.v_stride[1] == 0)) ||
-          (P > 1 && y.seq_len > 1 && (y.k_stride[2] == 0 || y.v_stride[2] == 0)) ||
-          (g.num_pages > 1 && (g.k_page_stride == 0 || g.v_page_stride == 0)))
-        return KVC_E_ARG;
-      continue;
-    }
     if (!dests) continue;  // contiguous k_out / v_out
     const kvc_dest_t& d = dests[l];
     if (d.reserved != 0 || d.in_place != 0) return KVC_E_ARG;
@@ -301,6 +315,79 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
     const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
                          span(y.v_out, dsize, d.v_stride, es, rowb)};
     if (ranges_meet(dst, src)) return KVC_E_ARG;
+  }
+  return KVC_OK;
+}
+
+// kvc_plan_ragged / kvc_launch_ragged (include/kvc.h, "Ragged paged batches"): every host record
+// under a layer's rules, the layers' segment fields set to (fill) or compared with (launch) the
+// envelope of their records, then plan_impl and the page checks on that envelope.
+// ragged == nullptr: plan_paged_impl without destinations.
+static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
+                            const kvc_ragged_t* ragged, int nl, kvc_plan_info_t* info,
+                            bool fill) {
+  if (!ragged) return plan_paged_impl(p, layers, pages, nullptr, nl, info, fill);
+  if (!p || nl < 0 || (nl > 0 && (!layers || !pages)) || p->batch < 1) return KVC_E_ARG;
+  if (p->external_index || (p->flags & (KVC_FLAG_SHARED_INDEX | KVC_FLAG_GATHER_FIXED |
+                                        KVC_FLAG_GATHER_SELECTED)))
+    return KVC_E_ARG;
+  for (int l = 0; l < nl; ++l) {
+    const kvc_ragged_t& r = ragged[l];
+    if (!r.host || !r.dev || ((uintptr_t)r.host & 3u) || ((uintptr_t)r.dev & 15u))
+      return KVC_E_ARG;
+    if (pages[l].in_place != 1) return KVC_E_ARG;
+    kvc_layer_t e = layers[l];  // the envelope
+    e.seq_len = e.zone_start = e.zone_len = e.n_select = e.sink_len = e.tail_start = 0;
+    e.tail_len = e.pool_kernel = 0;
+    e.score_mode = KVC_SCORE_NORM;
+    int64_t max_out = 0;
+    bool selects = false;
+    for (int b = 0; b < p->batch; ++b) {
+      const kvc_seq_t& q = r.host[b];
+      const int S = q.seq_len;
+      if (S < 0 || q.zone_start < 0 || q.zone_len < 0 || (int64_t)q.zone_start + q.zone_len > S ||
+          q.n_select < 0 || q.n_select > q.zone_len || q.sink_len < 0 || q.sink_len > S ||
+          q.tail_start < 0 || q.tail_len < 0 || (int64_t)q.tail_start + q.tail_len > S ||
+          (q.score_mode != KVC_SCORE_NORM && q.score_mode != KVC_SCORE_SNAPKV) ||
+          q.reserved[0] != 0 || q.reserved[1] != 0 ||
+          (int64_t)q.sink_len + q.n_select + q.tail_len != q.n_out)
+        return KVC_E_ARG;
+      kvc_layer_t y = e;  // the record as a layer: the row-map rule's argument
+      y.zone_start = q.zone_start, y.zone_len = q.zone_len, y.n_select = q.n_select;
+      y.sink_len = q.sink_len, y.tail_start = q.tail_start, y.tail_len = q.tail_len;
+      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
+      const bool sel = layer_selects(y);
+      selects |= sel;
+      e.seq_len = S > e.seq_len ? S : e.seq_len;
+      e.zone_len = q.zone_len > e.zone_len ? q.zone_len : e.zone_len;
+      e.n_select = q.n_select > e.n_select ? q.n_select : e.n_select;
+      e.pool_kernel = q.pool_kernel > e.pool_kernel ? q.pool_kernel : e.pool_kernel;
+      if (sel && q.score_mode == KVC_SCORE_SNAPKV) e.score_mode = KVC_SCORE_SNAPKV;
+      max_out = q.n_out > max_out ? q.n_out : max_out;
+    }
+    if (selects && e.n_select >= e.zone_len) {  // the envelope of a selecting record selects
+      e.zone_len = e.n_select + 1;
+      e.seq_len = e.zone_len > e.seq_len ? e.zone_len : e.seq_len;
+    }
+    e.tail_len = (int32_t)(max_out - e.n_select);
+    kvc_layer_t& y = layers[l];
+    if (fill) {
+      y.seq_len = e.seq_len, y.zone_start = 0, y.zone_len = e.zone_len, y.n_select = e.n_select;
+      y.sink_len = 0, y.tail_start = 0, y.tail_len = e.tail_len;
+      y.pool_kernel = e.pool_kernel, y.score_mode = e.score_mode;
+    } else if (y.seq_len != e.seq_len || y.zone_start != 0 || y.zone_len != e.zone_len ||
+               y.n_select != e.n_select || y.sink_len != 0 || y.tail_start != 0 ||
+               y.tail_len != e.tail_len || y.pool_kernel != e.pool_kernel ||
+               y.score_mode != e.score_mode) {
+      return KVC_E_ARG;
+    }
+  }
+  int rc = plan_impl(p, layers, nl, info, fill);
+  if (rc != KVC_OK) return rc;
+  for (int l = 0; l < nl; ++l) {
+    if (layers[l].n_out == 0) continue;
+    rc = paged_layer_check(p, layers[l], pages[l], false);
+    if (rc != KVC_OK) return rc;
   }
   return KVC_OK;
 }
@@ -602,6 +689,100 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
   return rc;
 }
 
+// SELECT of a ragged chunk: launch_select's choice of kernel class by the call's longest
+// (envelope) zone, with the instances that read each row's bounds from its record.
+template <int KC>
+static int launch_select_ragged(const RaggedChunk& C, int cn, int H, int BH, int dt, int order,
+                                int algo, const char* norms, int64_t nstride, int32_t* idx,
+                                int64_t istride, bool long_zone, char* scratch, uint32_t* status,
+                                hipStream_t s, const uint32_t* tmax) {
+  typedef typename DTypeTraits<KC>::key_t KeyT;
+  const dim3 rows_grid((unsigned)(cn * BH));
+  const int n_cap = (int)nstride;
+  if (long_zone) {
+    const int64_t rb = (int64_t)sel_scratch_row_bytes(n_cap, KC);
+    if (n_cap > kZoneMaxGlobal)
+      return launch_k(select_long_ragged_kernel<KC>, rows_grid, dim3(kSelThreads), 0, s, C, H, BH,
+                      dt, order, algo, norms, nstride, idx, istride, scratch, rb, n_cap, status);
+    if (algo == KVC_ALGO_STABLE)
+      return launch_k(select_global_ragged_kernel<KC, true>, rows_grid, dim3(kSelThreads), 0, s, C,
+                      H, BH, dt, order, algo, norms, nstride, idx, istride, kWaveSeg, scratch, rb,
+                      n_cap, status);
+    return launch_k(select_global_ragged_kernel<KC>, rows_grid, dim3(kSelThreads), 0, s, C, H, BH,
+                    dt, order, algo, norms, nstride, idx, istride, kWaveSeg, scratch, rb, n_cap,
+                    status);
+  }
+  const auto go = [&](auto stable) {
+    constexpr bool ST = decltype(stable)::value;
+    if (n_cap <= kSmallZone) {
+      int cap;
+      const size_t lds = small_sel_lds(n_cap, (int)sizeof(KeyT), &cap);
+      return launch_k(select_ragged_kernel<KC, kSelThreadsSmall, ST>, rows_grid,
+                      dim3(kSelThreadsSmall), lds, s, C, H, BH, dt, order, algo, norms, nstride,
+                      idx, istride, kWaveSegSmall, n_cap, cap, status, tmax);
+    }
+    return launch_k(select_ragged_kernel<KC, kSelThreads, ST>, rows_grid, dim3(kSelThreads), 0, s,
+                    C, H, BH, dt, order, algo, norms, nstride, idx, istride, kWaveSeg, n_cap, 0,
+                    status, tmax);
+  };
+  if (algo == KVC_ALGO_STABLE) return go(std::true_type());
+  return go(std::false_type());
+}
+
+// One chunk of <= kPagedLayers ragged layers: SCORE, SELECT and GATHER as three kernels, grids and
+// kernel classes by the layers' envelopes (what plan_ragged_impl left in the table), each row's
+// bounds from its device record.
+template <int DT, int NC>
+static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& info,
+                               const kvc_layer_t* layers, const kvc_pages_t* pages,
+                               const kvc_ragged_t* ragged, int nl, int c0, int cn, char* w,
+                               hipStream_t s) {
+  constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
+  const int H = p->heads, BH = p->batch * p->heads;
+  char* norms = w + info.norm_offset;
+  int32_t* idx = reinterpret_cast<int32_t*>(w + info.index_offset);
+  const int64_t nstride = info.norm_row_stride, istride = info.index_row_stride;
+  RaggedChunk C;
+  memset(&C, 0, sizeof(C));
+  memcpy(C.l, layers + c0, (size_t)cn * sizeof(kvc_layer_t));
+  memcpy(C.p, pages + c0, (size_t)cn * sizeof(kvc_pages_t));
+  for (int l = 0; l < cn; ++l) C.s[l] = ragged[c0 + l].dev;
+  const int64_t tile_base = layers[c0].tile0;
+  const int64_t tile_end = c0 + cn < nl ? (int64_t)layers[c0 + cn].tile0 : info.score_tiles;
+  bool sel = false, long_zone = false, snap = false;
+  int64_t max_out = 0;
+  for (int l = c0; l < c0 + cn; ++l) {
+    sel |= layers[l].n_select > 0;
+    snap |= layer_selects(layers[l]) && layers[l].score_mode == KVC_SCORE_SNAPKV;
+    long_zone |= layer_selects(layers[l]) && layers[l].zone_len > kZoneMax;
+    max_out = layers[l].n_out > max_out ? layers[l].n_out : max_out;
+  }
+  uint32_t* status = p->device_status;
+  uint32_t* tmax = snap ? reinterpret_cast<uint32_t*>(w + tmax_offset(info, p->dtype)) : nullptr;
+  int rc = KVC_OK;
+  if ((p->phases & KVC_PHASE_SCORE) && tile_end > tile_base) {  // some envelope selects
+    int64_t zmax = 0;  // the chunk's longest selecting envelope zone
+    for (int l = c0; l < c0 + cn; ++l)
+      if (layer_selects(layers[l]) && layers[l].zone_len > zmax) zmax = layers[l].zone_len;
+    const int64_t per_block = (int64_t)kRaggedTiles * kTile;
+    rc = launch_k(score_ragged_kernel<DT, NC>,
+                  dim3((unsigned)(cn * BH), (unsigned)((zmax + per_block - 1) / per_block)),
+                  dim3(score_waves(NC) * 64), 0, s, C, H, BH, norms, nstride, tmax,
+                  nstride / kTile, status);
+  }
+  if (rc != KVC_OK) return rc;
+  if ((p->phases & KVC_PHASE_SELECT) && sel) {
+    char* scratch = w + round_up(info.index_offset + (size_t)info.rows * istride * 4, 256);
+    rc = launch_select_ragged<KC>(C, cn, H, BH, DT, p->order, p->algo, norms, nstride, idx,
+                                  istride, long_zone, scratch, status, s, tmax);
+  }
+  if (rc != KVC_OK) return rc;
+  if ((p->phases & KVC_PHASE_GATHER) && max_out > 0)
+    rc = launch_k(gather_ragged_kernel<DT, NC>, dim3((unsigned)(cn * BH)), dim3(kGatherThreads), 0,
+                  s, C, H, BH, static_cast<const int32_t*>(idx), istride, status);
+  return rc;
+}
+
 // kvc_debug_select_capacity: the 512-thread SELECT / SELECT_GATHER kernels of one chunk with a
 // caller-chosen zone capacity (the device-side bounds check's test hook)
 static int debug_select_impl(const kvc_params_t* p, const kvc_layer_t* layers, int nl, char* w,
@@ -852,6 +1033,36 @@ int kvc_launch_paged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc
       return with_nc(nc, [&](auto ncv) {
         return launch_chunk<decltype(dt)::value, decltype(ncv)::value>(p, info, layers, nl, c0,
                                                                        cn, w, s, dests, pages);
+      });
+    });
+  }
+  return rc;
+}
+
+int kvc_plan_ragged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, int num_layers, kvc_plan_info_t* info) {
+  return kvc::plan_ragged_impl(params, layers, pages, ragged, num_layers, info, true);
+}
+
+int kvc_launch_ragged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
+                      const kvc_ragged_t* ragged, int nl, void* ws, size_t ws_bytes,
+                      kvc_stream_t stream) {
+  using namespace kvc;
+  if (!ragged) return kvc_launch_paged(p, layers, pages, nullptr, nl, ws, ws_bytes, stream);
+  kvc_plan_info_t info;
+  int rc = plan_ragged_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, nl, &info, false);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0) return KVC_OK;
+  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  const int nc = p->head_dim * esize(p->dtype) / 16;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kPagedLayers) {
+    const int cn = nl - c0 < kPagedLayers ? nl - c0 : kPagedLayers;
+    rc = with_dtype(p->dtype, [&](auto dt) {
+      return with_nc(nc, [&](auto ncv) {
+        return launch_chunk_ragged<decltype(dt)::value, decltype(ncv)::value>(
+            p, info, layers, pages, ragged, nl, c0, cn, w, s);
       });
     });
   }

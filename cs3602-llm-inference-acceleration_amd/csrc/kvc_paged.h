@@ -175,6 +175,12 @@ __global__ void __launch_bounds__(score_waves(NC) * 64)
 // rows have src == dst and are not touched, so pages holding only sink rows may be shared between
 // sequences.
 // An in-place store through a page id outside [0, num_pages) is DROPPED (loads are clamped).
+//
+// Ragged batches (kvc_ragged.h) run the same schedule with every (b, h) row's n_out, sink, zone
+// and tail taken from its own record.  Nothing above changes: the argument is about the logical
+// rows of ONE sequence behind ONE table row, the row-map rule is applied to every record, and no
+// step uses that the sequences of a layer have a common length -- gather_passes needs nothing
+// from memory beyond what this paragraph already asks.
 // ---------------------------------------------------------------------------------------------
 // Rows of one (b, h) sequence of a paged K and V.
 struct PagedRows {

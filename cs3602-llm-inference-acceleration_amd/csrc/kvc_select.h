@@ -780,19 +780,16 @@ __device__ int partition_long(KeyT* key, uint32_t* idx, uint32_t* spos, uint32_t
   return cut;
 }
 
+// The selection of workspace row `row`, whose zone_len, n_select, score_mode and pool_kernel are
+// ly's (the layer's, or a ragged row's own: kvc_ragged.h); ssc / sc: the kernel's LDS scalars.
 template <int KC>
-__global__ void __launch_bounds__(kSelThreads)
-    select_long_kernel(const LayerChunk T, int BH, int dt, int order, int algo,
-                       const char* __restrict__ norms, int64_t norm_stride,
-                       int32_t* __restrict__ out_idx, int64_t idx_stride,
-                       char* __restrict__ scratch, int64_t scratch_row_bytes, int n_cap,
-                       uint32_t* status) {
+__device__ __forceinline__ void select_long_body(
+    const kvc_layer_t* ly, int row, int dt, int order, int algo, const char* __restrict__ norms,
+    int64_t norm_stride, int32_t* __restrict__ out_idx, int64_t idx_stride,
+    char* __restrict__ scratch, int64_t scratch_row_bytes, int n_cap, uint32_t* status,
+    SelScalars<typename DTypeTraits<KC>::key_t>& ssc, LongScalars& sc) {
   typedef typename DTypeTraits<KC>::key_t KeyT;
   constexpr int ESZ = DTypeTraits<KC>::esz;
-  __shared__ SelScalars<KeyT> ssc;
-  __shared__ LongScalars sc;
-  const kvc_layer_t* ly = T.l + blockIdx.x / BH;
-  const int row = ly->row0 + (int)(blockIdx.x % BH);
   const int n = ly->zone_len, k = ly->n_select;
   int32_t* out = out_idx + (int64_t)row * idx_stride;
   if (k > 0 && k >= n) {  // keeps its whole zone: no scratch, any length (as in select_body)
@@ -886,6 +883,20 @@ __global__ void __launch_bounds__(kSelThreads)
     if (f) out[run + __popcll(bf & lanemask_lt(lane))] = pos;
     run += __popcll(bf);
   }
+}
+
+template <int KC>
+__global__ void __launch_bounds__(kSelThreads)
+    select_long_kernel(const LayerChunk T, int BH, int dt, int order, int algo,
+                       const char* __restrict__ norms, int64_t norm_stride,
+                       int32_t* __restrict__ out_idx, int64_t idx_stride,
+                       char* __restrict__ scratch, int64_t scratch_row_bytes, int n_cap,
+                       uint32_t* status) {
+  __shared__ SelScalars<typename DTypeTraits<KC>::key_t> ssc;
+  __shared__ LongScalars sc;
+  const kvc_layer_t* ly = T.l + blockIdx.x / BH;
+  select_long_body<KC>(ly, ly->row0 + (int)(blockIdx.x % BH), dt, order, algo, norms, norm_stride,
+                       out_idx, idx_stride, scratch, scratch_row_bytes, n_cap, status, ssc, sc);
 }
 
 }  // namespace kvc

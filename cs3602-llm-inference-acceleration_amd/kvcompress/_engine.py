@@ -238,7 +238,7 @@ def execute(jobs: List[Segments], out_list: list, order: int, algo: int):
                 raise ValueError(f"kvcompress: the stable tie policy selects from zones of at most "
                                  f"{STABLE_MAX_ZONE} positions (layer {j.layer_idx}: "
                                  f"{j.zone_len}); use the reference policy for longer zones")
-    if _defer(jobs, lambda: execute(jobs, out_list, order, algo), out_list):
+    if _defer(jobs, lambda: execute(jobs, out_list, order, algo), out_list, (order, algo)):
         return  # a call with `out`: dest_call() launches once every destination is checked
     if jobs[0].paged is not None:  # compress_paged's jobs, checked by it
         from .paged import run_jobs
@@ -295,10 +295,13 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H, dests=None, pages=None):
+def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None):
     """Plan one table and allocate its workspace.  The table itself travels in the kernels'
     arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    if pages is not None:
+    if ragged is not None:
+        rc, info = N.plan_ragged(params, table, pages, ragged)
+        N.check(rc, "kvc_plan_ragged")
+    elif pages is not None:
         rc, info = N.plan_paged(params, table, pages, dests)
         N.check(rc, "kvc_plan_paged")
     elif dests is None:
@@ -319,7 +322,7 @@ def _upload(params, table, device, js, B, H, dests=None, pages=None):
     return ws, info
 
 
-def _launch(params, table, ws, info, stream, phases, dests=None, pages=None):
+def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, ragged=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
@@ -330,7 +333,10 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None):
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        if pages is not None:
+        if ragged is not None:
+            rc = N.launch_ragged(params, table, pages, ragged, ws.data_ptr(),
+                                 int(info.workspace_bytes), stream.cuda_stream)
+        elif pages is not None:
             rc = N.launch_paged(params, table, pages, dests, ws.data_ptr(),
                                 int(info.workspace_bytes), stream.cuda_stream)
         elif dests is None:
@@ -341,7 +347,8 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None):
                                stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch_paged" if pages is not None else
+        N.check(rc, "kvc_launch_ragged" if ragged is not None else
+                "kvc_launch_paged" if pages is not None else
                 "kvc_launch" if dests is None else "kvc_launch_dest")
         if _timer is not None:
             _timer.records.append((name, a, b))
@@ -773,11 +780,13 @@ class _DestCall:
     pair or None.  While the method runs, execute() / execute_shared() launch nothing: they give
     every job its layer's destination and park the launch in `pending` [(jobs, run, out_list)];
     `done` collects the layers whose engine job took its destination.  `rollback` holds what undoes
-    the method's side effects (h2o_attention's manager update) when a check then fails."""
-    __slots__ = ("dests", "done", "pending", "rollback")
+    the method's side effects (h2o_attention's manager update) when a check then fails.  `how[i]`
+    is the (order, algo) of pending[i], or None for a launch with caller-provided indices."""
+    __slots__ = ("dests", "done", "pending", "rollback", "how")
 
     def __init__(self, dests):
         self.dests, self.done, self.pending, self.rollback = dests, set(), [], []
+        self.how = []
 
 
 def dest_call_active():
@@ -793,9 +802,9 @@ def on_dest_error(undo):
         ctx.rollback.append(undo)
 
 
-def _defer(jobs, run, out_list):
+def _defer(jobs, run, out_list, how=None):
     """Inside a call with `out` (dest_call): give the jobs their layers' destinations, park the
-    launch and return True; otherwise False."""
+    launch (and its (order, algo), when the engine selects) and return True; otherwise False."""
     ctx = getattr(_dest_state, "ctx", None)
     if ctx is None:
         return False
@@ -806,6 +815,7 @@ def _defer(jobs, run, out_list):
             j.dest_checked = True
             ctx.done.add(j.layer_idx)
     ctx.pending.append((jobs, run, out_list))
+    ctx.how.append(how)
     return True
 
 

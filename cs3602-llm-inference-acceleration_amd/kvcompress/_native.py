@@ -58,6 +58,16 @@ PAGES_DTYPE = np.dtype([
 ])
 assert PAGES_DTYPE.itemsize == 48
 
+# struct kvc_seq / kvc_ragged (include/kvc.h: ragged paged batches) -- 48 / 16 bytes
+SEQ_DTYPE = np.dtype([
+    ("seq_len", "<i4"), ("zone_start", "<i4"), ("zone_len", "<i4"), ("n_select", "<i4"),
+    ("sink_len", "<i4"), ("tail_start", "<i4"), ("tail_len", "<i4"), ("score_mode", "<i4"),
+    ("pool_kernel", "<i4"), ("n_out", "<i4"), ("reserved", "<i4", (2,)),
+])
+assert SEQ_DTYPE.itemsize == 48
+RAGGED_DTYPE = np.dtype([("host", "<u8"), ("dev", "<u8")])
+assert RAGGED_DTYPE.itemsize == 16
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -97,7 +107,7 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_source_digest",
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
            "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
-           "kvc_plan_paged", "kvc_launch_paged")
+           "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged")
 
 _lib = None
 
@@ -144,6 +154,13 @@ def lib():
         L.kvc_launch_paged.restype = i32
         L.kvc_launch_paged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32, vp,
                                        ctypes.c_size_t, vp]
+    if hasattr(L, "kvc_plan_ragged"):  # additive within ABI 4, like the paged entries
+        L.kvc_plan_ragged.restype = i32
+        L.kvc_plan_ragged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32,
+                                      ctypes.POINTER(PlanInfo)]
+        L.kvc_launch_ragged.restype = i32
+        L.kvc_launch_ragged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32, vp,
+                                        ctypes.c_size_t, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -243,6 +260,34 @@ def launch_paged(params, table, pages, dests, ws_ptr, ws_bytes, stream_ptr):
                                   _opt(pages, PAGES_DTYPE, len(table)),
                                   _opt(dests, DEST_DTYPE, len(table)), len(table), ws_ptr,
                                   ws_bytes, stream_ptr)
+
+
+def _need_ragged_entries():
+    if not hasattr(lib(), "kvc_plan_ragged"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_plan_ragged / kvc_launch_ragged (built "
+                                 "before ragged batches); they need the current library")
+
+
+def plan_ragged(params, table, pages, ragged):
+    """kvc_plan_ragged: `ragged` is a RAGGED_DTYPE array, one entry per layer (host / device
+    addresses of params.batch SEQ_DTYPE records each), or None (= kvc_plan_paged).  Overwrites the
+    table's segment fields with the envelope of each layer's records."""
+    info = PlanInfo()
+    _need_ragged_entries()
+    rc = lib().kvc_plan_ragged(ctypes.byref(params), table.ctypes.data,
+                               _opt(pages, PAGES_DTYPE, len(table)),
+                               _opt(ragged, RAGGED_DTYPE, len(table)), len(table),
+                               ctypes.byref(info))
+    return rc, info
+
+
+def launch_ragged(params, table, pages, ragged, ws_ptr, ws_bytes, stream_ptr):
+    """kvc_launch_ragged (ragged None = kvc_launch_paged without destinations)."""
+    _need_ragged_entries()
+    return lib().kvc_launch_ragged(ctypes.byref(params), table.ctypes.data,
+                                   _opt(pages, PAGES_DTYPE, len(table)),
+                                   _opt(ragged, RAGGED_DTYPE, len(table)), len(table), ws_ptr,
+                                   ws_bytes, stream_ptr)
 
 
 def attn_accumulate(params, table, stream_ptr):

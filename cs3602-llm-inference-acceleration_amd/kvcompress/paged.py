@@ -10,6 +10,11 @@ The method's own Python runs over stand-in tensors of every layer's shape (nothi
 to the cache is allocated; the methods only read shapes), inside the deferred-call context of
 the `out` kwarg (_engine.dest_call): every job it records is checked, mapped onto its PagedKV and
 only then launched with kvc_launch_paged.  No plan cache, no call memo.
+
+A PagedKV may carry a length per sequence (a ragged layer: the rows of a continuous batch).  The
+method then runs once per distinct per-layer length profile over B = 1 stand-ins, every job it
+records becomes the kvc_seq_t record of its (layer, sequence), and the call is one
+kvc_launch_ragged per launch group, whatever B is (plan_ragged, _compress_ragged).
 """
 import numpy as np
 import torch
@@ -23,8 +28,47 @@ class PagedKV:
     with a contiguous last dim and 16-byte aligned pointers and strides; never copied), an int32
     `block_table` [B, >= ceil(seq_len / page_size)] on the same device, and the common logical
     length `seq_len` of its B sequences.  vLLM's [N, P, H, D] cache is `cache.permute(0, 2, 1, 3)`;
-    the halves of a fused [2, N, ...] buffer are `kv[0]` and `kv[1]`."""
-    __slots__ = ("k_pool", "v_pool", "block_table", "seq_len")
+    the halves of a fused [2, N, ...] buffer are `kv[0]` and `kv[1]`.
+
+    A RAGGED layer gives `seq_len` as B non-negative ints instead -- a list, a tuple, a numpy
+    integer array or a CPU integer tensor, one length per row of the block table, as a
+    continuous-batching server has them.  The lengths are host data (the methods' size arithmetic
+    is host Python): a device tensor is refused rather than silently synchronised on.  `seq_len`
+    then reads back as the tuple of lengths, `seq_lens` is that tuple for either kind of layer,
+    and `shape` is [B, H, max(seq_lens), D]: the envelope of the B sequences, of which sequence b
+    fills rows [0, seq_lens[b])."""
+    __slots__ = ("k_pool", "v_pool", "block_table", "seq_len", "seq_lens")
+
+    @staticmethod
+    def _lengths(seq_len):
+        """None for an int length (checked by the caller), else the tuple of per-sequence ints."""
+        if isinstance(seq_len, (bool, int)):
+            return None
+        if isinstance(seq_len, torch.Tensor):
+            if seq_len.device.type != "cpu":
+                raise TypeError(f"PagedKV: per-sequence lengths must be host data (a list, a numpy "
+                                f"array or a CPU tensor); got a tensor on {seq_len.device} -- the "
+                                "methods' size arithmetic runs on the host, and reading a device "
+                                "tensor would synchronise silently")
+            if seq_len.dim() != 1 or seq_len.dtype == torch.bool or seq_len.is_floating_point() \
+                    or seq_len.is_complex():
+                raise ValueError("PagedKV: per-sequence lengths must be a 1-D integer tensor; got "
+                                 f"{seq_len.dtype} {tuple(seq_len.shape)}")
+            vals = seq_len.tolist()
+        elif isinstance(seq_len, np.ndarray):
+            if seq_len.ndim != 1 or seq_len.dtype.kind not in "iu":
+                raise ValueError("PagedKV: per-sequence lengths must be a 1-D integer array; got "
+                                 f"{seq_len.dtype} {seq_len.shape}")
+            vals = seq_len.tolist()
+        elif isinstance(seq_len, (list, tuple)):
+            vals = list(seq_len)
+        else:
+            return None
+        for x in vals:
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 0:
+                raise ValueError("PagedKV: per-sequence lengths must be non-negative ints, got "
+                                 f"{x!r}")
+        return tuple(int(x) for x in vals)
 
     def __init__(self, k_pool, v_pool, block_table, seq_len):
         for name, t in (("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
@@ -40,8 +84,11 @@ class PagedKV:
         if npg < 1 or H < 1 or D < 1 or P < 1 or P > 65536 or P & (P - 1):
             raise ValueError(f"PagedKV: page_size must be a power of two in [1, 65536] and the "
                              f"pool non-empty; got pools of shape {tuple(k_pool.shape)}")
-        if isinstance(seq_len, bool) or not isinstance(seq_len, int) or seq_len < 0:
-            raise ValueError(f"PagedKV: seq_len must be a non-negative int, got {seq_len!r}")
+        lens = self._lengths(seq_len)
+        if lens is None and (isinstance(seq_len, bool) or not isinstance(seq_len, int) or
+                             seq_len < 0):
+            raise ValueError(f"PagedKV: seq_len must be a non-negative int (or one per sequence), "
+                             f"got {seq_len!r}")
         es = k_pool.element_size()
         for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
             if (t.stride(3) != 1 and D > 1) or (D * es) % 16 or any(
@@ -56,10 +103,14 @@ class PagedKV:
             raise ValueError("PagedKV: block_table must be an int32 [B, pages per sequence] "
                              "tensor with a contiguous last dim; got "
                              f"{block_table.dtype} {tuple(block_table.shape)}")
-        need = -(-seq_len // P)
+        if lens is not None and len(lens) != block_table.size(0):
+            raise ValueError(f"PagedKV: {len(lens)} sequence lengths for a block table of "
+                             f"{block_table.size(0)} rows")
+        longest = seq_len if lens is None else max(lens, default=0)
+        need = -(-longest // P)
         if block_table.size(0) < 1 or block_table.size(1) < need:
             raise ValueError(f"PagedKV: block_table {tuple(block_table.shape)} holds fewer than "
-                             f"the {need} pages of {seq_len} rows of {P}")
+                             f"the {need} pages of {longest} rows of {P}")
         if not (k_pool.is_cuda and v_pool.is_cuda and block_table.is_cuda) or \
                 not (k_pool.device == v_pool.device == block_table.device):
             raise ValueError("PagedKV: pools and block table must be on one ROCm device (no CPU "
@@ -69,24 +120,37 @@ class PagedKV:
             if t.data_ptr() % 16:
                 raise ValueError(f"PagedKV: {name} pointer not 16-byte aligned (a pool is never "
                                  "copied)")
-        self.k_pool, self.v_pool, self.block_table, self.seq_len = k_pool, v_pool, block_table, \
-            seq_len
+        self.k_pool, self.v_pool, self.block_table = k_pool, v_pool, block_table
+        self.seq_len = seq_len if lens is None else lens
+        self.seq_lens = (seq_len,) * block_table.size(0) if lens is None else lens
+
+    @property
+    def ragged(self):
+        """True when the layer carries a length per sequence."""
+        return not isinstance(self.seq_len, int)
 
     @property
     def shape(self):
-        """The [B, H, seq_len, D] of the dense tensors the table describes."""
-        return (self.block_table.size(0), self.k_pool.size(1), self.seq_len, self.k_pool.size(3))
+        """The [B, H, seq_len, D] of the dense tensors the table describes; for a ragged layer
+        seq_len is the longest sequence's (the envelope: sequence b fills rows [0, seq_lens[b]))."""
+        return (self.block_table.size(0), self.k_pool.size(1), max(self.seq_lens),
+                self.k_pool.size(3))
 
     @property
     def page_size(self):
         return self.k_pool.size(2)
 
-    def to_dense(self, n=None):
+    def to_dense(self, n=None, b=None):
         """(K, V) [B, H, n, D] of the first n (default seq_len) logical rows, by torch indexing:
-        a convenience for tests and debugging, not on the hot path."""
-        n = self.seq_len if n is None else n
+        a convenience for tests and debugging, not on the hot path.  With `b`: sequence b's rows
+        alone, [1, H, n, D], n by default its own length (a ragged layer needs `b` or `n`)."""
+        if n is None:
+            if b is None and self.ragged:
+                raise ValueError("PagedKV.to_dense: a ragged layer needs b (one sequence) or n")
+            n = self.seq_len if b is None else self.seq_lens[b]
+        table = self.block_table if b is None else self.block_table[b:b + 1]
         pos = torch.arange(n, device=self.k_pool.device)
-        pg = self.block_table[:, :max(-(-n // self.page_size), 1)].long()
+        pg = table[:, :max(-(-n // self.page_size), 1)].long()
         pg = pg[:, pos // self.page_size]            # [B, n] page of every row
         slot = pos % self.page_size                  # [n]
         return tuple(pool[pg, :, slot].permute(0, 2, 1, 3) for pool in (self.k_pool, self.v_pool))
@@ -133,6 +197,14 @@ def compress_paged(method, layers, out="inplace", **kwargs):
     K_dst[:, :, :n] / V_dst[:, :, :n] (dense views under the `out` kwarg's rules), whatever the
     method does with it, its pool is not written, and those views are returned; None = in place.
 
+    Ragged layers (PagedKV with a length per sequence): when any layer is ragged, all layers share
+    one batch B (an int layer counts as B equal lengths), and the result is what the method gives
+    on each sequence alone -- every layer restricted to block_table[b:b+1] and seq_lens[b], layer
+    indices (skip_layers, pyramid_kv's schedule) unchanged.  In place only; returns per layer the
+    list of B new lengths.  The kernel launches do not depend on B: one SCORE / SELECT / GATHER
+    set per (device, dtype, H, D, order, algo) group (kvc_launch_ragged).  Caller-provided indices
+    (strategy="random", h2o_attention's heavy hitters) and dense `out` pairs raise TypeError.
+
     Everything is checked before anything launches: an error leaves every pool untouched."""
     return E._checked_call(lambda: _compress_paged(method, layers, out, kwargs))
 
@@ -165,6 +237,8 @@ def _compress_paged(method, layers, out, kwargs):
                 raise TypeError(f"layer {i}: out entry must be a (K_dst, V_dst) pair or None")
     else:
         raise TypeError(f"out must be \"inplace\" or a list, got {type(out).__name__}")
+    if any(pk.ragged for pk in layers):
+        return _compress_ragged(fn, layers, dests, kwargs)
     kvl = [_stand_in(pk) for pk in layers]
     seen = {}
     for i, (pk, (k, v), d) in enumerate(zip(layers, kvl, dests)):  # before anything is enqueued
@@ -224,6 +298,176 @@ def _compress_paged(method, layers, out, kwargs):
             n = n_of.get(i, 0)
             result.append((d[0].narrow(2, 0, n), d[1].narrow(2, 0, n)))
     return result
+
+
+def plan_ragged(fn, lens, geometry, kwargs, check=True):
+    """Host planning of a ragged call (no launch, no device copy): the method's own Python runs
+    once per distinct per-layer length profile over B = 1 stand-ins, inside the deferred-call
+    context, and every job or move it records becomes the kvc_seq_t record of its (layer,
+    sequence).  `lens[l][b]` are the lengths, `geometry[l]` = (H, D, dtype, device) of layer l's
+    stand-ins; check=False skips the engine's tensor checks (host-only models of the mapping).
+    Returns (records [L][B] SEQ_DTYPE, no-op where nothing moves; how: {(layer, b): (order, algo)
+    of an engine job, or None for a copy-only move}; new lengths [L][B])."""
+    rec, spans, new_len = _plan_spans(fn, lens, geometry, kwargs, check)
+    return rec, {(li, b): how for li, bs, how in spans for b in bs}, new_len
+
+
+def _plan_spans(fn, lens, geometry, kwargs, check):
+    """plan_ragged with `how` per span: [(layer, [b, ...], (order, algo) | None)], one entry per
+    (profile, layer) that an engine job or a move touches."""
+    L, B = len(lens), len(lens[0])
+    rec = np.zeros((L, B), dtype=N.SEQ_DTYPE)
+    for li in range(L):  # the no-op record: every row a sink row
+        rec[li]["seq_len"] = rec[li]["sink_len"] = rec[li]["n_out"] = lens[li]
+    new_len = [list(l) for l in lens]
+    spans = []
+    profiles = {}
+    for b in range(B):
+        profiles.setdefault(tuple(l[b] for l in lens), []).append(b)
+    raw = getattr(fn, "__wrapped__", fn)  # the method's own Python: no call memo, no `out`
+    dests = ["inplace"] * L
+    bases = {}  # one stand-in storage per (dtype, device): K rows at 0, V rows behind them
+    for (_, _, dtype, device), l in zip(geometry, lens):
+        bases[(dtype, device)] = max(bases.get((dtype, device), 1), max(l))
+    bases = {k: (torch.empty(2 * n, dtype=k[0], device=k[1]), n) for k, n in bases.items()}
+    for prof, bs in profiles.items():
+        kvl = []
+        for (H, D, dtype, device), S in zip(geometry, prof):
+            base, half = bases[(dtype, device)]
+            kvl.append((base.as_strided((1, H, S, D), (0, 0, 1, 0), 0),
+                        base.as_strided((1, H, S, D), (0, 0, 1, 0), half)))
+        ctx = E._DestCall(dests)
+        prev = getattr(E._dest_state, "ctx", None)
+        try:
+            E._dest_state.ctx = ctx
+            try:
+                res = list(raw(list(kvl), **kwargs))  # launches nothing: see _engine._defer()
+            finally:
+                E._dest_state.ctx = prev
+            moves = E._dest_moves(kvl, res, dests, ctx)
+            found = [(j, how) for (jobs, _, _), how in zip(ctx.pending, ctx.how) for j in jobs]
+            found += [(j, None) for j in moves]
+            done = set()
+            for j, how in found:
+                li = j.layer_idx
+                if j.keys is not kvl[li][0] or j.k_dest is not j.keys or li in done:
+                    raise RuntimeError(f"layer {li}: the method built a job that compress_paged "
+                                       "cannot map onto its PagedKV")
+                if j.ext_index is not None or (how is None and j.n_select):
+                    raise TypeError(
+                        "compress_paged: ragged layers (per-sequence lengths) do not take "
+                        "caller-provided indices (strategy=\"random\", h2o_attention's heavy "
+                        "hitters): compress such sequences one by one")
+                done.add(li)
+                E._check_dest(j)  # in place on a stand-in: the segment order
+                if check:
+                    E._check_tensors(j)
+                n = j.sink_len + j.n_select + j.tail_len
+                rec[li, bs] = (prof[li], j.zone_start, j.zone_len, j.n_select, j.sink_len,
+                               j.tail_start, j.tail_len, j.score_mode, j.pool_kernel, n, (0, 0))
+                spans.append((li, bs, how))
+                row = new_len[li]
+                for b in bs:
+                    row[b] = n
+            for li in set(range(L)) - done:  # untouched, or already the front view
+                n = int(res[li][0].size(2))
+                if n != prof[li]:
+                    row = new_len[li]
+                    for b in bs:
+                        row[b] = n
+        except BaseException:
+            for undo in reversed(ctx.rollback):
+                undo()
+            raise
+    return rec, spans, new_len
+
+
+def _compress_ragged(fn, layers, dests, kwargs):
+    """compress_paged on layers with per-sequence lengths: plan_ragged, one upload of every
+    group's records, one kvc_launch_ragged per (device, dtype, H, D, order, algo) group.  In a
+    group's launch every (layer, sequence) that belongs to another group -- or to none -- has the
+    no-op record."""
+    L = len(layers)
+    if any(d != "inplace" for d in dests):
+        raise TypeError("compress_paged: ragged layers (per-sequence lengths) are compacted in "
+                        "place only; dense out= pairs are not supported")
+    if kwargs.get("strategy") == "random":
+        raise TypeError("compress_paged: ragged layers (per-sequence lengths) do not take "
+                        "caller-provided indices (strategy=\"random\")")
+    B = layers[0].block_table.size(0)
+    seen = {}
+    for i, pk in enumerate(layers):
+        if pk.block_table.size(0) != B:
+            raise ValueError(f"layer {i}: {pk.block_table.size(0)} sequences, layer 0 has {B}: the "
+                             "layers of a ragged call share one batch")
+        for name, t in (("K", pk.k_pool), ("V", pk.v_pool)):
+            if t.data_ptr() in seen:
+                raise ValueError(f"layer {i}: {name} pool shares its memory with "
+                                 f"{seen[t.data_ptr()]}: not compacted in place")
+            seen[t.data_ptr()] = f"layer {i}'s {name} pool"
+    rec, spans, new_len = _plan_spans(
+        fn, [pk.seq_lens for pk in layers],
+        [(pk.k_pool.size(1), pk.k_pool.size(3), pk.k_pool.dtype, pk.k_pool.device)
+         for pk in layers], kwargs, True)
+    # launch groups: engine jobs by their (order, algo); copy-only moves ride in a group of their
+    # geometry (any order / algo: nothing is selected)
+    geos = [(pk.k_pool.get_device(), pk.k_pool.dtype, pk.k_pool.size(1), pk.k_pool.size(3))
+            for pk in layers]
+    groups = {}
+    for li, bs, how in spans:
+        if how is not None:
+            groups.setdefault(geos[li] + how, {}).setdefault(li, []).extend(bs)
+    for li, bs, how in spans:
+        if how is None:
+            key = next((k for k in groups if k[:4] == geos[li]),
+                       geos[li] + (N.KVC_ASC, N.KVC_ALGO_SORT))
+            groups.setdefault(key, {}).setdefault(li, []).extend(bs)
+    if not groups:
+        return new_len
+    # every group's records, all of them in one array per device: one host-to-device copy
+    plans, per_dev = [], {}
+    for key, members in groups.items():
+        lis = sorted(members)
+        seqs = np.zeros((len(lis), B), dtype=N.SEQ_DTYPE)
+        for i, li in enumerate(lis):
+            seqs[i]["seq_len"] = seqs[i]["sink_len"] = seqs[i]["n_out"] = layers[li].seq_lens
+            seqs[i, members[li]] = rec[li, members[li]]
+        per_dev.setdefault(key[0], []).append(seqs)
+        plans.append((key, lis, len(per_dev[key[0]]) - 1))
+    host, dev, start = {}, {}, {}
+    for device, arrs in per_dev.items():
+        host[device] = np.concatenate([a.reshape(-1) for a in arrs])
+        start[device] = np.cumsum([0] + [a.size for a in arrs]) * N.SEQ_DTYPE.itemsize
+        dev[device] = torch.from_numpy(host[device].view(np.uint8)).to(
+            torch.device("cuda", device))
+    launches = []
+    for (device, dtype, H, D, order, algo), lis, slot in plans:  # plan (and check) every group
+        with torch.cuda.device(device):
+            p = E._params(dtype, B, H, D, order, algo, False)
+            n = len(lis)
+            table = np.zeros(n, dtype=N.LAYER_DTYPE)
+            pages = np.zeros(n, dtype=N.PAGES_DTYPE)
+            ragged = np.zeros(n, dtype=N.RAGGED_DTYPE)
+            off = int(start[device][slot])
+            for i, li in enumerate(lis):
+                pk = layers[li]
+                kp, vp, bt = pk.k_pool, pk.v_pool, pk.block_table
+                t = table[i]
+                t["k"] = t["k_out"] = kp.data_ptr()
+                t["v"] = t["v_out"] = vp.data_ptr()
+                t["k_stride"] = (0, kp.stride(1), kp.stride(2))
+                t["v_stride"] = (0, vp.stride(1), vp.stride(2))
+                pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
+                            kp.size(0), 1, 0)
+                step = off + i * B * N.SEQ_DTYPE.itemsize
+                ragged[i] = (host[device].ctypes.data + step, dev[device].data_ptr() + step)
+            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged)
+            launches.append((device, p, table, ws, info, pages, ragged))
+    for device, p, table, ws, info, pages, ragged in launches:
+        with torch.cuda.device(device):
+            E._launch(p, table, ws, info, torch.cuda.current_stream(device), p.phases, None, pages,
+                      ragged)
+    return new_len
 
 
 def run_jobs(jobs, order, algo):

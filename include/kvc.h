@@ -196,7 +196,8 @@ const char* kvc_status_string(int status);
 /* SHA-256 (hex) of the sources this library was compiled from (csrc/kvc.hip, then the headers it
  * includes -- kvc_common.h, kvc_serial.h, kvc_device_util.h, kvc_score.h, kvc_snapkv_keys.h,
  * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h,
- * kvc_paged.h -- then include/kvc.h, in that order), or "unknown" for builds that do not set it --
+ * kvc_paged.h, kvc_ragged.h -- then include/kvc.h, in that order), or "unknown" for builds that
+ * do not set it --
  * lets a caller (and tests/test_abi.py) check that a shipped binary matches its source tree. */
 const char* kvc_source_digest(void);
 
@@ -342,6 +343,84 @@ int kvc_plan_paged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pa
 int kvc_launch_paged(const kvc_params_t* params, const kvc_layer_t* layers,
                      const kvc_pages_t* pages, const kvc_dest_t* dests, int num_layers,
                      void* workspace, size_t workspace_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ragged paged batches (additive within ABI 4: no existing struct, size or entry changes; a
+ * library without these two entries does not export them).
+ *
+ * A continuous-batching server's block table has a length per row.  With a kvc_ragged_t per layer,
+ * every (layer, b) of a paged call has its own segments: the result is that of kvc_launch_paged on
+ * each sequence alone (batch = 1, the table row of b, the segments of record b), in ONE launch set
+ * whose kernel count does not depend on the batch.
+ *
+ * kvc_seq_t is the part of kvc_layer_t that the methods' size arithmetic decides, per sequence.
+ * Every layer gives `batch` records twice: `host` (read by plan and launch, validated there) and
+ * `dev` (device memory holding the same records, read by the kernels when they RUN).  The library
+ * never allocates, copies or synchronises: the caller uploads the records.  A captured launch
+ * follows the device records at replay time, as it follows the block table; rewritten records
+ * must stay inside what was planned (below), which the library cannot check at replay.
+ *
+ * Rules (KVC_E_ARG otherwise): every layer is paged and in place (kvc_pages_t.in_place == 1,
+ * k_out == k, v_out == v); external_index, KVC_FLAG_SHARED_INDEX and KVC_FLAG_GATHER_FIXED /
+ * _SELECTED are refused; host and dev are non-NULL, host 4-byte and dev 16-byte aligned (the
+ * kernels read a record as three 16-byte words); every record obeys the
+ * rules of a layer -- segment bounds inside its own seq_len, 0 <= n_select <= zone_len, a known
+ * score_mode, n_out == sink_len + n_select + tail_len, reserved 0, the in-place row-map rule of
+ * kvc_dest_t's contract -- and table_stride >= ceil(max seq_len / page_size).  Zone-length limits
+ * (KVC_E_TOO_LONG) apply to the envelope below.
+ *
+ * For a ragged layer the segment fields of kvc_layer_t are OUTPUTS of kvc_plan_ragged: it
+ * overwrites them with the ENVELOPE of the layer's records,
+ *     seq_len   = max seq_len          zone_start = 0        sink_len = 0    tail_start = 0
+ *     zone_len  = max zone_len  (*)    n_select   = max n_select
+ *     tail_len  = max n_out - max n_select   (so n_out = max n_out)
+ *     score_mode = KVC_SCORE_SNAPKV if a selecting record has it, else KVC_SCORE_NORM
+ *     pool_kernel = max pool_kernel
+ *     (*) max n_select + 1 when some record selects (0 < n_select < zone_len) although
+ *         max n_select == max zone_len: the envelope of a layer with a selecting record selects.
+ * and then fills n_out, row0, tile0, unit0 and kvc_plan_info_t exactly as kvc_plan does for that
+ * envelope layer: workspace layout, grids and the kernel choice are those of the longest
+ * sequence.  kvc_launch_ragged expects the table as kvc_plan_ragged left it.  k, v, k_out, v_out
+ * and the strides stay the caller's inputs.
+ *
+ * A NO-OP record is sink_len = n_out = seq_len, every other field 0: nothing is scored, selected
+ * or copied (sink rows are never touched in place).  It stands for a sequence that passes through
+ * or that this launch leaves to another one.
+ *
+ * Device safety: the kernels take a row's bounds from its device record.  A record whose zone is
+ * longer than the launch's selection capacity sets KVC_DEV_SELECT_BOUNDS as on every path.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct kvc_seq {
+  int32_t seq_len;
+  int32_t zone_start;
+  int32_t zone_len;
+  int32_t n_select;
+  int32_t sink_len;
+  int32_t tail_start;
+  int32_t tail_len;
+  int32_t score_mode;  /* enum kvc_score */
+  int32_t pool_kernel;
+  int32_t n_out;       /* sink_len + n_select + tail_len */
+  int32_t reserved[2]; /* 0 */
+} kvc_seq_t;           /* 48 bytes */
+
+typedef struct kvc_ragged {
+  const kvc_seq_t* host; /* `batch` records in host memory                        */
+  const kvc_seq_t* dev;  /* the same `batch` records in device memory             */
+} kvc_ragged_t;          /* 16 bytes */
+
+/* kvc_plan_paged for ragged layers: ragged[i] belongs to layers[i] / pages[i].  ragged == NULL
+ * behaves exactly like kvc_plan_paged(params, layers, pages, NULL, ...).  Pure host function. */
+int kvc_plan_ragged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, int num_layers, kvc_plan_info_t* info);
+
+/* kvc_launch_paged for ragged layers (ragged == NULL: exactly kvc_launch_paged without dests).
+ * Re-validates table, pages and host records as kvc_plan_ragged does.  The kernels receive the
+ * layer and page tables and the device record pointers by value (chunks of 32 layers); SCORE,
+ * SELECT and GATHER are kernels of their own that read each row's bounds from its record. */
+int kvc_launch_ragged(const kvc_params_t* params, const kvc_layer_t* layers,
+                      const kvc_pages_t* pages, const kvc_ragged_t* ragged, int num_layers,
+                      void* workspace, size_t workspace_bytes, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |

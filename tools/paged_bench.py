@@ -12,6 +12,17 @@ comparison to watch is paged SCORE over dense SCORE at P = 128, nhpd (`score_vs_
 GPU box only.
 
   python tools/paged_bench.py [--shapes headline,decode] [--rounds 5] [--layers 32] [--out FILE]
+
+--ragged measures batches with a length per sequence (kvc_launch_ragged) instead, P = 16, nhpd:
+  a_batch_vs_loop   B = 8 and 64 sequences of 600..16 384 rows: one ragged call against the loop
+                    of B single-sequence calls, host and GPU time separately;
+  b_envelope        a 16 384-row sequence beside seven of 600, alone, and the seven alone: what
+                    the short rows pay for the long row's grid and kernel class;
+  c_uniform         the headline call as a list of equal lengths (ragged kernels) and as an int
+                    (the existing kernels): the price of the record indirection;
+  d_host_planning   host planning time against the number of distinct length profiles.
+`ms_call` is event to event around whole calls (host-bound when the GPU is idle between
+launches), `gpu_ms*` the summed kernel durations of a call's launches, `host_us` the enqueue time.
 """
 import argparse
 import json
@@ -93,13 +104,138 @@ def host_us(fn, reps):
     return round(dt / reps * 1e6, 1)
 
 
+# ---- --ragged: per-sequence lengths in one launch set ("Ragged paged batches") --------
+def ragged_pools(L, lens, heads, P, gen):
+    """L layers of one nhpd pool pair holding len(lens) sequences behind a shuffled [B, pages]
+    table (entries past a sequence's last page are 0: valid, never read)."""
+    npp = [-(-n // P) for n in lens]
+    n = sum(npp) + SPARE
+    out = []
+    for _ in range(L):
+        pools = [torch.empty(n, heads, P, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+                 for _ in range(2)]
+        perm = torch.randperm(n, generator=gen, device=DEV).to(torch.int32)
+        table = torch.zeros(len(lens), max(npp), dtype=torch.int32, device=DEV)
+        at = 0
+        for b, c in enumerate(npp):
+            table[b, :c] = perm[at:at + c]
+            at += c
+        out.append((pools[0], pools[1], table))
+    return out
+
+
+def gpu_ms(fn, reps):
+    """Kernel time of one call: the SCORE / SELECT / GATHER durations of all its launches, summed
+    (fenceless events around every launch), per call."""
+    t = E.PhaseTimer(split=True, steps=E.PhaseTimer.THREE, fenceless=True)
+    E.set_phase_timer(t)
+    try:
+        for _ in range(reps):
+            fn()
+        d = t.durations_ms()
+    finally:
+        E.set_phase_timer(None)
+    return {k: round(sum(v) / reps, 4) for k, v in d.items()}
+
+
+def measure(fn, reps, rounds):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    ts = [sample(fn, reps) for _ in range(rounds)]
+    g = gpu_ms(fn, reps)
+    return dict(ms_call_median=round(statistics.median(ts), 4), ms_call_min=round(min(ts), 4),
+                ms_call_max=round(max(ts), 4), gpu_ms_score=g.get("score", 0.0),
+                gpu_ms_select=g.get("select", 0.0), gpu_ms_gather=g.get("gather", 0.0),
+                gpu_ms=round(sum(g.values()), 4), host_us=host_us(fn, reps), reps=reps,
+                rounds=rounds)
+
+
+def spread(B, lo=600, hi=16384):
+    """B lengths from lo to hi, geometrically spaced (many short sequences, few long ones)."""
+    if B == 1:
+        return [hi]
+    return [int(round(lo * (hi / lo) ** (i / (B - 1)))) for i in range(B)]
+
+
+def ragged_main(args):
+    from kvcompress import paged as PG
+    L, P, gen = args.layers, 16, torch.Generator(device=DEV).manual_seed(0)
+    lines = []
+
+    def emit(**kw):
+        lines.append(dict(tool="paged_bench", mode="ragged", method=METHOD, layers=L, page_size=P,
+                          dtype="bf16", D=D, **kw))
+        print(json.dumps(lines[-1]), flush=True)
+
+    def calls(pools, rows, lens):
+        """(the ragged call, the loop of single-sequence calls) over table rows `rows`."""
+        rag = [PagedKV(k, v, t[rows], [lens[b] for b in rows]) for k, v, t in pools]
+        one = [[PagedKV(k, v, t[b:b + 1], lens[b]) for k, v, t in pools] for b in rows]
+        return (lambda: compress_paged(METHOD, rag, **KW),
+                lambda: [compress_paged(METHOD, x, **KW) for x in one])
+
+    # (a) a batch against the loop of single-sequence calls (the only thing a PagedKV with one
+    # int length can run); heads = 8 keeps the 64-sequence pools near 40 GiB
+    heads = 8
+    lens = spread(64)
+    pools = ragged_pools(L, lens, heads, P, gen)
+    for B in (8, 64):
+        rows = list(range(0, 64, 64 // B))
+        rag, loop = calls(pools, rows, lens)
+        for name, fn in (("ragged", rag), ("loop", loop)):
+            emit(part="a_batch_vs_loop", B=B, H=heads, variant=name, tokens=sum(lens[b] for b in rows),
+                 **measure(fn, 2 if B == 64 else 4, args.rounds))
+    del pools
+    torch.cuda.empty_cache()
+    # (b) what the envelope costs: one long sequence beside seven short ones
+    lens = [16384] + [600] * 7
+    pools = ragged_pools(L, lens, heads, P, gen)
+    for name, rows in (("A_long_and_seven_short", list(range(8))), ("B_long_alone", [0]),
+                       ("C_seven_short", list(range(1, 8)))):
+        rag, _ = calls(pools, rows, lens)
+        emit(part="b_envelope", batch=name, B=len(rows), H=heads, **measure(rag, 8, args.rounds))
+    del pools
+    torch.cuda.empty_cache()
+    # (c) uniform lengths at the paged headline geometry: the list runs the ragged kernels, the
+    # int the existing ones -- the price of the record indirection
+    pools = ragged_pools(L, [16384], H, P, gen)
+    for name, fn in (("list_of_equal_lengths", calls(pools, [0], [16384])[0]),
+                     ("int", lambda: compress_paged(
+                         METHOD, [PagedKV(k, v, t, 16384) for k, v, t in pools], **KW))):
+        emit(part="c_uniform", B=1, H=H, S=16384, variant=name, **measure(fn, 4, args.rounds))
+    del pools
+    torch.cuda.empty_cache()
+    # (d) host planning time against the number of distinct length profiles (no GPU work)
+    fn = get_compress_fn(METHOD)
+    geo = [(heads, D, torch.bfloat16, DEV)] * L
+    for distinct in (1, 8, 64):
+        base = spread(distinct)
+        lens = [base[b % distinct] for b in range(64)]
+        ts = []
+        for _ in range(7):
+            t0 = time.perf_counter()
+            PG.plan_ragged(fn, [lens] * L, geo, KW)
+            ts.append((time.perf_counter() - t0) * 1e6)
+        emit(part="d_host_planning", B=64, distinct_profiles=distinct,
+             plan_us_median=round(statistics.median(ts), 1), plan_us_min=round(min(ts), 1))
+    if args.out:
+        with open(args.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="headline,decode")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--out", default="", help="append the JSON lines to this file as well")
+    ap.add_argument("--ragged", action="store_true",
+                    help="measure ragged batches (per-sequence lengths) instead of the shapes")
     args = ap.parse_args()
+    if args.ragged:
+        return ragged_main(args)
     L = args.layers
     gen = torch.Generator(device=DEV).manual_seed(0)
     dense_fn = get_compress_fn(METHOD)
