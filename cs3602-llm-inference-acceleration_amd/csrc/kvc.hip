@@ -47,7 +47,11 @@ namespace kvc {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline int esize(int dtype) { return dtype == KVC_F32 ? 4 : 2; }
+// STORAGE element size: addressing, alignment, span checks, GATHER units
+static inline int esize(int dtype) { return dtype == KVC_F32 ? 4 : is_fp8(dtype) ? 1 : 2; }
+// SCORE element size: the norm region, the tile maxima and the selection's key class (fp8 keys
+// are scored as their exact bf16 upcast)
+static inline int score_esize(int dtype) { return esize(score_dt(dtype)); }
 // Calls f(std::integral_constant<int, DT>) for the call's storage dtype (validated by plan_impl).
 template <typename F>
 static int with_dtype(int dtype, F&& f) {
@@ -59,18 +63,31 @@ static int with_dtype(int dtype, F&& f) {
   return f(std::integral_constant<int, KVC_F32>());
 #endif
 }
+// with_dtype over the K/V storage dtypes: the fp8 formats as well (the attention entries, whose
+// tensors are never fp8, keep with_dtype)
+template <typename F>
+static int with_kv_dtype(int dtype, F&& f) {
+#ifdef KVC_ISA_PROBE  // (bf16 instantiations only: no fp8 kernel to run)
+  if (is_fp8(dtype)) return KVC_E_DTYPE;
+#else
+  if (dtype == KVC_F8E4M3) return f(std::integral_constant<int, KVC_F8E4M3>());
+  if (dtype == KVC_F8E5M2) return f(std::integral_constant<int, KVC_F8E5M2>());
+#endif
+  return with_dtype(dtype, f);
+}
 static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // one row of the global selection scratch (SelArrays for n_cap positions), 256-B aligned rows
 static inline size_t sel_scratch_row_bytes(int n_cap, int dtype) {
-  if (n_cap > kZoneMaxGlobal) return round_up(sel_long_bytes(n_cap, esize(dtype)), 256);
-  return round_up(sel_bytes(n_cap, esize(dtype), n_cap / 2 + 1), 256);
+  if (n_cap > kZoneMaxGlobal) return round_up(sel_long_bytes(n_cap, score_esize(dtype)), 256);
+  return round_up(sel_bytes(n_cap, score_esize(dtype), n_cap / 2 + 1), 256);
 }
 
 static int plan_impl(const kvc_params_t* p, kvc_layer_t* layers, int nl, kvc_plan_info_t* info,
                      bool fill) {
   if (!p || nl < 0 || (nl > 0 && !layers)) return KVC_E_ARG;
-  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16 && p->dtype != KVC_F32) return KVC_E_DTYPE;
+  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16 && p->dtype != KVC_F32 && !is_fp8(p->dtype))
+    return KVC_E_DTYPE;
   if (p->batch < 1 || p->heads < 1 || p->head_dim < 1) return KVC_E_ARG;
   if (p->order != KVC_ASC && p->order != KVC_DESC) return KVC_E_ARG;
   if (p->algo != KVC_ALGO_SORT && p->algo != KVC_ALGO_TOPK && p->algo != KVC_ALGO_STABLE)
@@ -93,6 +110,8 @@ static int plan_impl(const kvc_params_t* p, kvc_layer_t* layers, int nl, kvc_pla
   // 64..1024-byte rows: every pythia geometry (D 32/64/80/128/256) in bf16, fp16 and fp32
   if (nc != 4 && nc != 8 && nc != 10 && nc != 16 && nc != 20 && nc != 32 && nc != 64)
     return KVC_E_HEADDIM;
+  // fp8 rows: D = 64 / 128 / 256 only (the widths the fp8 kernels are built and tested for)
+  if (is_fp8(p->dtype) && nc != 4 && nc != 8 && nc != 16) return KVC_E_HEADDIM;
   const int64_t BH = (int64_t)p->batch * p->heads;
   if (BH * nl > 0x7FFFFFFF) return KVC_E_ARG;
   int64_t tiles = 0, units = 0, max_zone = 0, max_sel = 0;
@@ -150,7 +169,7 @@ static int plan_impl(const kvc_params_t* p, kvc_layer_t* layers, int nl, kvc_pla
     info->index_row_stride = (int64_t)round_up((size_t)(max_sel > 0 ? max_sel : 1), 16);
     size_t off = 0;
     info->norm_offset = off;
-    off = round_up(off + (size_t)rows * info->norm_row_stride * es, 256);
+    off = round_up(off + (size_t)rows * info->norm_row_stride * score_esize(p->dtype), 256);
     info->index_offset = off;
     off = round_up(off + (size_t)rows * info->index_row_stride * 4, 256);
     if (max_zone > kZoneMax)  // selection scratch rows for zones longer than the LDS limit
@@ -429,6 +448,21 @@ static int with_nc(int nc, F&& f) {
 #endif
 }
 
+// with_nc for the call's storage dtype: fp8 rows exist in the 64 / 128 / 256-byte widths only
+template <int DT, typename F>
+static int with_nc_dt(int nc, F&& f) {
+  if constexpr (is_fp8(DT)) {
+    switch (nc) {
+      case 4: return f(std::integral_constant<int, 4>());
+      case 8: return f(std::integral_constant<int, 8>());
+      case 16: return f(std::integral_constant<int, 16>());
+      default: return KVC_E_HEADDIM;
+    }
+  } else {
+    return with_nc(nc, f);
+  }
+}
+
 // Keys are read once (non-temporal loads) and outputs written once (non-temporal stores): they
 // would otherwise evict useful lines from the Infinity Cache.
 // (grid: one tile per wave, score_waves(NC) tiles per workgroup)
@@ -586,6 +620,8 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                         const kvc_pages_t* pages = nullptr) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
+  constexpr int SDT = score_dt(DT);  // the selection's runtime dtype (bf16 for fp8 rows)
+  constexpr bool F8 = is_fp8(DT);    // the fused kernel's row copy: bytes, no NaN rewrite
   const int H = p->heads, BH = p->batch * p->heads;
   char* norms = w + info.norm_offset;
   int32_t* idx = reinterpret_cast<int32_t*>(w + info.index_offset);
@@ -640,8 +676,8 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
         if (n_cap <= kSmallZone) {
           int cap;
           const size_t lds = small_sel_lds(n_cap, ks, &cap);
-          return launch_k(select_gather_kernel<KC, kSelThreadsSmall, NC, ST>, rows_grid,
-                          dim3(kSelThreadsSmall), lds, s, T, H, BH, DT, p->order, p->algo, norms,
+          return launch_k(select_gather_kernel<KC, kSelThreadsSmall, NC, ST, true, F8>, rows_grid,
+                          dim3(kSelThreadsSmall), lds, s, T, H, BH, SDT, p->order, p->algo, norms,
                           nstride, kWaveSegSmall, n_cap, cap, status, 0, tmax);
         }
         // fewer rows than CUs (e.g. 4 layers per GPU of an 8-way layer split): one row per CU
@@ -660,19 +696,19 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
         // cfg5 pyramid ones)
         if constexpr (!ST) {
           if (plain)
-            return launch_k(select_gather_kernel<KC, kSelThreads, NC, ST, true>, grid,
-                            dim3(kSelThreads), 0, s, T, H, BH, DT, p->order, p->algo, norms,
+            return launch_k(select_gather_kernel<KC, kSelThreads, NC, ST, true, F8>, grid,
+                            dim3(kSelThreads), 0, s, T, H, BH, SDT, p->order, p->algo, norms,
                             nstride, kWaveSeg, n_cap, 0, status, split, tmax);
         }
-        return launch_k(select_gather_kernel<KC, kSelThreads, NC, ST, false>, grid,
-                        dim3(kSelThreads), 0, s, T, H, BH, DT, p->order, p->algo, norms, nstride,
+        return launch_k(select_gather_kernel<KC, kSelThreads, NC, ST, false, F8>, grid,
+                        dim3(kSelThreads), 0, s, T, H, BH, SDT, p->order, p->algo, norms, nstride,
                         kWaveSeg, n_cap, 0, status, split, tmax);
       };
       return p->algo == KVC_ALGO_STABLE ? go(std::true_type()) : go(std::false_type());
     }
     char* scratch = w + round_up(info.index_offset + (size_t)info.rows * istride * 4, 256);
     uint64_t* st = stamps ? stamps + (size_t)layers[c0].row0 * 32 : nullptr;
-    rc = launch_select<KC>(T, cn, BH, DT, p->order, p->algo, norms, nstride, idx, istride,
+    rc = launch_select<KC>(T, cn, BH, SDT, p->order, p->algo, norms, nstride, idx, istride,
                            long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
@@ -773,7 +809,7 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
   if (rc != KVC_OK) return rc;
   if ((p->phases & KVC_PHASE_SELECT) && sel) {
     char* scratch = w + round_up(info.index_offset + (size_t)info.rows * istride * 4, 256);
-    rc = launch_select_ragged<KC>(C, cn, H, BH, DT, p->order, p->algo, norms, nstride, idx,
+    rc = launch_select_ragged<KC>(C, cn, H, BH, score_dt(DT), p->order, p->algo, norms, nstride, idx,
                                   istride, long_zone, scratch, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
@@ -802,20 +838,22 @@ static int debug_select_impl(const kvc_params_t* p, const kvc_layer_t* layers, i
   int32_t* idx = reinterpret_cast<int32_t*>(w + info.index_offset);
   const dim3 grid((unsigned)(nl * BH));
   const int nc = p->head_dim * esize(p->dtype) / 16;
-  return with_dtype(p->dtype, [&](auto dt) {
+  return with_kv_dtype(p->dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
+    constexpr int SDT = score_dt(DT);
     int cap;
     const size_t lds = small_sel_lds(zone_cap, (int)sizeof(typename DTypeTraits<KC>::key_t), &cap);
     if (p->phases == KVC_PHASE_SELECT)
       return launch_k(select_kernel<KC, kSelThreadsSmall>, grid, dim3(kSelThreadsSmall), lds, s,
-                      T, BH, DT, p->order, p->algo, norms, info.norm_row_stride, idx,
+                      T, BH, SDT, p->order, p->algo, norms, info.norm_row_stride, idx,
                       info.index_row_stride, kWaveSegSmall, zone_cap, cap,
                       static_cast<uint64_t*>(nullptr), p->device_status,
                       static_cast<const uint32_t*>(nullptr));
-    return with_nc(nc, [&](auto ncv) {
-      return launch_k(select_gather_kernel<KC, kSelThreadsSmall, decltype(ncv)::value>, grid,
-                      dim3(kSelThreadsSmall), lds, s, T, H, BH, DT, p->order, p->algo, norms,
+    return with_nc_dt<DT>(nc, [&](auto ncv) {
+      return launch_k(select_gather_kernel<KC, kSelThreadsSmall, decltype(ncv)::value, false, true,
+                                           is_fp8(DT)>,
+                      grid, dim3(kSelThreadsSmall), lds, s, T, H, BH, SDT, p->order, p->algo, norms,
                       info.norm_row_stride, kWaveSegSmall, zone_cap, cap, p->device_status, 0,
                       static_cast<const uint32_t*>(nullptr));
     });
@@ -979,7 +1017,7 @@ const char* kvc_status_string(int s) {
   switch (s) {
     case KVC_OK: return "ok";
     case KVC_E_ARG: return "invalid argument";
-    case KVC_E_DTYPE: return "unsupported dtype (bf16/fp16/fp32 only)";
+    case KVC_E_DTYPE: return "unsupported dtype (bf16/fp16/fp32, fp8 e4m3fn/e5m2 K/V only)";
     case KVC_E_HEADDIM: return "unsupported head_dim";
     case KVC_E_ALIGN: return "pointer or stride not 16-byte aligned";
     case KVC_E_TOO_LONG: return "scored zone longer than kvc_max_zone_len()";
@@ -1029,8 +1067,8 @@ int kvc_launch_paged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc
   const int step = pages ? kPagedLayers : kArgLayers;  // layers per argument chunk
   for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
     const int cn = nl - c0 < step ? nl - c0 : step;
-    rc = with_dtype(p->dtype, [&](auto dt) {
-      return with_nc(nc, [&](auto ncv) {
+    rc = with_kv_dtype(p->dtype, [&](auto dt) {
+      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
         return launch_chunk<decltype(dt)::value, decltype(ncv)::value>(p, info, layers, nl, c0,
                                                                        cn, w, s, dests, pages);
       });
@@ -1059,8 +1097,8 @@ int kvc_launch_ragged(const kvc_params_t* p, const kvc_layer_t* layers, const kv
   const int nc = p->head_dim * esize(p->dtype) / 16;
   for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kPagedLayers) {
     const int cn = nl - c0 < kPagedLayers ? nl - c0 : kPagedLayers;
-    rc = with_dtype(p->dtype, [&](auto dt) {
-      return with_nc(nc, [&](auto ncv) {
+    rc = with_kv_dtype(p->dtype, [&](auto dt) {
+      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
         return launch_chunk_ragged<decltype(dt)::value, decltype(ncv)::value>(
             p, info, layers, pages, ragged, nl, c0, cn, w, s);
       });

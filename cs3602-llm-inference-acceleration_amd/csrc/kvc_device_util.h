@@ -71,6 +71,22 @@ struct DTypeTraits<KVC_F32> {
   static constexpr int esz = 4;
   typedef uint32_t key_t;
 };
+// fp8 (OCP e4m3fn / e5m2) STORAGE: 1-byte elements that only SCORE decodes and GATHER moves as
+// bytes.  Everything behind SCORE -- the norm region, the tile maxima, the sort keys -- is that of
+// the exact bf16 upcast: the SCORE dtype below.
+template <>
+struct DTypeTraits<KVC_F8E4M3> {
+  static constexpr int esz = 1;
+  typedef uint16_t key_t;
+};
+template <>
+struct DTypeTraits<KVC_F8E5M2> {
+  static constexpr int esz = 1;
+  typedef uint16_t key_t;
+};
+__host__ __device__ constexpr bool is_fp8(int dt) { return dt == KVC_F8E4M3 || dt == KVC_F8E5M2; }
+// The dtype a storage dtype's keys are scored, stored in the norm region and selected in.
+__host__ __device__ constexpr int score_dt(int dt) { return is_fp8(dt) ? KVC_BF16 : dt; }
 
 template <int DT>
 __device__ __forceinline__ float load_dt(const char* base, int i) {

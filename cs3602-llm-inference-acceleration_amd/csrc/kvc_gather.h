@@ -203,7 +203,8 @@ __device__ __forceinline__ void gather_row(const kvc_layer_t* __restrict__ ly, i
 // ---------------------------------------------------------------------------------------------
 // L0T: level 0 may keep its rank tables in the idx region (run_chain); the instance without that
 // code runs launches where it does not pay (launch_chunk)
-template <int KC, int NT, int NC, bool STABLE = false, bool L0T = true>
+// F8: the rows are fp8 storage (either format: the copy does not interpret them)
+template <int KC, int NT, int NC, bool STABLE = false, bool L0T = true, bool F8 = false>
 __global__ void __launch_bounds__(NT, sel_waves_per_eu(KC, NT))
     select_gather_kernel(const LayerChunk T, int H, int BH, int dt, int order, int algo,
                          const char* __restrict__ norms, int64_t norm_stride, int wave_seg,
@@ -226,13 +227,20 @@ __global__ void __launch_bounds__(NT, sel_waves_per_eu(KC, NT))
     n_cap = kZoneMax;
     cap = kSelCapBig<KeyT>;
   }
+  // The row copy runs in the STORAGE dtype: `dt` for 16- and 32-bit rows; fp8 rows (F8: NC chunks
+  // of 16 one-byte elements, moved verbatim) select as bf16 -- dt is KVC_BF16 -- and copy as bytes.
   if (copier) {
     // a row over the selecting workgroup's capacity is flagged there and left wholly unwritten
     // (KVC_DEV_SELECT_BOUNDS): its sink / tail rows are not copied either
-    if (selects && ly->zone_len <= MAXN && ly->zone_len <= n_cap)
-      with_dt<KC>(dt, [&](auto D) {
-        gather_row<D.value, NC, NT>(ly, r, H, nullptr, PART_FIXED);
-      });
+    if (selects && ly->zone_len <= MAXN && ly->zone_len <= n_cap) {
+      if constexpr (F8) {
+        gather_row<KVC_F8E4M3, NC, NT>(ly, r, H, nullptr, PART_FIXED);
+      } else {
+        with_dt<KC>(dt, [&](auto D) {
+          gather_row<D.value, NC, NT>(ly, r, H, nullptr, PART_FIXED);
+        });
+      }
+    }
     return;
   }
   const char* nrow = norms + (int64_t)(ly->row0 + r) * norm_stride * ESZ;
@@ -257,10 +265,15 @@ __global__ void __launch_bounds__(NT, sel_waves_per_eu(KC, NT))
                       // workgroup of a split row skips it too)
     __syncthreads();
   }
-  with_dt<KC>(dt, [&](auto D) {
-    gather_row<D.value, NC, NT>(ly, r, H, selects ? sel : nullptr,
-                                split_rows > 0 && selects ? PART_SELECTED : PART_ALL);
-  });
+  if constexpr (F8) {
+    gather_row<KVC_F8E4M3, NC, NT>(ly, r, H, selects ? sel : nullptr,
+                                   split_rows > 0 && selects ? PART_SELECTED : PART_ALL);
+  } else {
+    with_dt<KC>(dt, [&](auto D) {
+      gather_row<D.value, NC, NT>(ly, r, H, selects ? sel : nullptr,
+                                  split_rows > 0 && selects ? PART_SELECTED : PART_ALL);
+    });
+  }
 }
 
 }  // namespace kvc

@@ -36,6 +36,15 @@ int dtype_code(const at::Tensor& t) {
   }
 }
 
+// K / V tensors may also be fp8 (the OCP formats; attention tensors never are)
+int kv_dtype_code(const at::Tensor& t) {
+  switch (t.scalar_type()) {
+    case at::kFloat8_e4m3fn: return KVC_F8E4M3;
+    case at::kFloat8_e5m2: return KVC_F8E5M2;
+    default: return dtype_code(t);
+  }
+}
+
 bool as_tensor(PyObject* o, at::Tensor& out) {
   if (!THPVariable_Check(o)) return false;
   out = THPVariable_Unpack(o);
@@ -58,7 +67,7 @@ bool plain(const at::Tensor& t, int64_t row_bytes) {
 }  // namespace
 
 // (B, H, D, dtype, device, S_0 .. S_{L-1}) when every layer is a plain (K, V) pair on one ROCm
-// device -- 4-D, K.shape == V.shape, one (B, H, D) and dtype (bf16 / fp16 / fp32), contiguous,
+// device -- 4-D, K.shape == V.shape, one (B, H, D) and dtype (bf16 / fp16 / fp32 / fp8), contiguous,
 // 16-byte aligned rows -- else None (the call then takes the method's Python path).
 py::object scan(py::list kv) {
   const Py_ssize_t n = PyList_GET_SIZE(kv.ptr());
@@ -74,10 +83,10 @@ py::object scan(py::list kv) {
       return py::none();
     if (i == 0) {
       B = k.size(0), H = k.size(1), D = k.size(3);
-      dt = dtype_code(k);
+      dt = kv_dtype_code(k);
       dev = k.get_device();
       if (dt < 0) return py::none();
-    } else if (k.size(0) != B || k.size(1) != H || k.size(3) != D || dtype_code(k) != dt ||
+    } else if (k.size(0) != B || k.size(1) != H || k.size(3) != D || kv_dtype_code(k) != dt ||
                k.get_device() != dev) {
       return py::none();
     }

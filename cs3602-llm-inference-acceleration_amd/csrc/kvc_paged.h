@@ -59,6 +59,7 @@ __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kv
                                                  int64_t norm_stride, uint32_t* tmax,
                                                  int64_t tmax_stride, uint32_t* status) {
   constexpr int ESZ = DTypeTraits<DT>::esz;
+  constexpr int SDT = score_dt(DT);  // the norm region's dtype (bf16 for fp8 keys)
   constexpr int CP = score_cp(NC);
   constexpr int NPH = NC / CP;
   constexpr int ROWB = score_rowb(CP);
@@ -124,9 +125,9 @@ __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kv
 #pragma unroll
     for (int j = 1; j < 8; ++j) s = s + acc[j];
     const float r = __builtin_sqrtf(s);
-    char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * ESZ;
+    char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * DTypeTraits<SDT>::esz;
     if constexpr (DT != KVC_F32) {
-      bits = bits16_dt<DT>(r);
+      bits = bits16_dt<SDT>(r);
       __builtin_nontemporal_store((uint16_t)bits, reinterpret_cast<uint16_t*>(nrow) + tok0 + lane);
     } else {
       bits = f32_to_bits(r);

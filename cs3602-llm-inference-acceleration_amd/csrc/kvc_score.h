@@ -10,7 +10,34 @@ namespace kvc {
 // ---------------------------------------------------------------------------------------------
 template <int DT, int NC>
 __device__ __forceinline__ void accum_chunk(float (&acc)[8], const uint4 x, int gchunk) {
-  if constexpr (DT == KVC_F16) {
+  if constexpr (is_fp8(DT)) {
+    // chunk c holds the 16 elements 16c..16c+15: element e feeds accumulator e % 8, so dword q
+    // (elements 4q..4q+3) feeds accumulators 4*(q&1)..+3, dwords 0,1 before dwords 2,3 -- ascending
+    // element order per accumulator, torch.norm's order on the bf16 upcast.  The decode is gfx950's
+    // packed OCP converts (v_cvt_pk_f32_fp8 = e4m3fn, v_cvt_pk_f32_bf8 = e5m2): exact on all 256
+    // patterns, subnormals, NaN and e5m2's inf included.  test_fp8_score_gpu pins that: every
+    // pattern alone at every byte lane of an otherwise zero row, whose norm |x| * sqrt(D / 16)
+    // tells every magnitude of the format apart (a norm cannot see a sign; NaN and inf show as
+    // such).  x*x of an fp8 x is exact in fp32 either way.
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f32x2 lo, hi;
+      if constexpr (DT == KVC_F8E4M3) {
+        lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[q], false);
+        hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[q], true);
+      } else {
+        lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w[q], false);
+        hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w[q], true);
+      }
+      const int j0 = (q & 1) * 4;
+      acc[j0] = __builtin_fmaf(lo.x, lo.x, acc[j0]);
+      acc[j0 + 1] = __builtin_fmaf(lo.y, lo.y, acc[j0 + 1]);
+      acc[j0 + 2] = __builtin_fmaf(hi.x, hi.x, acc[j0 + 2]);
+      acc[j0 + 3] = __builtin_fmaf(hi.y, hi.y, acc[j0 + 3]);
+    }
+  } else if constexpr (DT == KVC_F16) {
     // NormTwoOps<Half, float> (binary_kernel_reduce): ONE accumulator in dim order; x*x is exact
     // in fp32 for an fp16 x, so the fma equals torch's acc + x*x.  (acc[1..7] stay 0: the final
     // lane sum adds +0 to a non-negative sum, which changes nothing.)
@@ -69,6 +96,7 @@ __device__ __forceinline__ void score_tile(const kvc_layer_t* ly, int row, int t
                                            char* wl, char* norms, int64_t norm_stride,
                                            uint32_t* tmax, int64_t tmax_stride) {
   constexpr int ESZ = DTypeTraits<DT>::esz;
+  constexpr int SDT = score_dt(DT);  // the norm region's dtype (bf16 for fp8 keys)
   constexpr int CP = score_cp(NC);  // 16-B chunks per token per phase
   constexpr int NPH = NC / CP;
   constexpr int ROWB = score_rowb(CP);  // padded LDS row: conflict-free ds_read_b128 per lane
@@ -118,11 +146,11 @@ __device__ __forceinline__ void score_tile(const kvc_layer_t* ly, int row, int t
 #pragma unroll
     for (int j = 1; j < 8; ++j) s = s + acc[j];
     const float r = __builtin_sqrtf(s);
-    char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * ESZ;
+    char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * DTypeTraits<SDT>::esz;
     // non-temporal: the select phase reads the norms back from the Infinity Cache, not from
     // this XCD's L2, so keeping them in L2 only evicts key lines (2.5% faster score pass)
     if constexpr (DT != KVC_F32) {
-      bits = bits16_dt<DT>(r);
+      bits = bits16_dt<SDT>(r);
       __builtin_nontemporal_store((uint16_t)bits, reinterpret_cast<uint16_t*>(nrow) + tok0 + lane);
     } else {
       bits = f32_to_bits(r);

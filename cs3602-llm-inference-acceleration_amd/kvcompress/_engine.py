@@ -47,8 +47,18 @@ class Segments:
     paged: Optional[object] = None
 
 
-_SUPPORTED = {torch.bfloat16: N.KVC_BF16, torch.float16: N.KVC_F16, torch.float32: N.KVC_F32}
-_ESIZE = {torch.bfloat16: 2, torch.float16: 2, torch.float32: 4}
+# fp8 K/V: the OCP formats only (gfx950's native fp8, dequantisation scale 1).  Keys are scored
+# as their exact bfloat16 upcast, rows are copied as bytes.  The fnuz
+# formats and raw uint8 / int8 tensors stay unsupported.
+_FP8 = {torch.float8_e4m3fn: N.KVC_F8E4M3, torch.float8_e5m2: N.KVC_F8E5M2}
+_SUPPORTED = {torch.bfloat16: N.KVC_BF16, torch.float16: N.KVC_F16, torch.float32: N.KVC_F32,
+              **_FP8}
+_ESIZE = {torch.bfloat16: 2, torch.float16: 2, torch.float32: 4,
+          torch.float8_e4m3fn: 1, torch.float8_e5m2: 1}
+
+
+def is_fp8(dtype):
+    return dtype in _FP8
 
 
 class HipEvent:
@@ -206,7 +216,8 @@ def _check_tensors(j: Segments):
     kd = k.dtype
     if kd not in _SUPPORTED or v.dtype != kd:
         raise TypeError(
-            f"kvcompress (MI355X HIP engine) supports bfloat16/float16/float32 K and V of one dtype; "
+            f"kvcompress (MI355X HIP engine) supports bfloat16/float16/float32 and fp8 "
+            f"(float8_e4m3fn/float8_e5m2) K and V of one dtype; "
             f"layer {j.layer_idx} has {kd}/{v.dtype}")
     shape = k.shape
     if len(shape) != 4 or v.shape != shape:

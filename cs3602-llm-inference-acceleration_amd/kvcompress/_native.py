@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libkvc.so")
 LIB_PATH = os.environ.get("KVC_LIB", LIB_PATH)
 
 KVC_F32, KVC_BF16, KVC_F16 = 0, 1, 2
+KVC_F8E4M3, KVC_F8E5M2 = 16, 17  # fp8 K/V storage (scored as bf16, copied as bytes)
 KVC_ASC, KVC_DESC = 0, 1
 KVC_ALGO_SORT, KVC_ALGO_TOPK, KVC_ALGO_STABLE = 0, 1, 2
 KVC_SCORE_NORM, KVC_SCORE_SNAPKV = 0, 1

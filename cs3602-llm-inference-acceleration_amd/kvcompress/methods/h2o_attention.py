@@ -240,6 +240,15 @@ def h2o_attention_compress(past_key_values, attention_scores: Optional[Tuple] = 
     past_key_values = list(normalize_kv_cache(past_key_values))
     if not past_key_values:
         return past_key_values
+    if h2o_manager is not None:
+        # fp8 K/V with a manager: refused before anything launches or the manager's state moves
+        # (its native replay and side-stream plans know the 16- and 32-bit dtypes only)
+        for layer_idx, (keys, values) in enumerate(past_key_values):
+            if E.is_fp8(keys.dtype) or E.is_fp8(values.dtype):
+                raise TypeError(
+                    f"kvcompress (MI355X HIP engine): h2o_attention with an H2OAttentionManager "
+                    f"does not take fp8 K/V (layer {layer_idx}: {keys.dtype}/{values.dtype}); "
+                    "call it without a manager, or keep the cache in bfloat16/float16/float32")
     if h2o_manager is not None and attention_scores is not None:
         out = _replay_step(past_key_values, attention_scores, h2o_manager, start_size,
                            heavy_hitter_size, recent_size, skip_layers)

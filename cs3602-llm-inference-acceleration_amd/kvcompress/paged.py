@@ -78,7 +78,8 @@ class PagedKV:
             raise ValueError("PagedKV: k_pool / v_pool must both be [num_pages, H, page_size, D]; "
                              f"got {tuple(k_pool.shape)} / {tuple(v_pool.shape)}")
         if k_pool.dtype not in E._SUPPORTED or v_pool.dtype != k_pool.dtype:
-            raise ValueError("PagedKV: pools must be bfloat16 / float16 / float32 and of one "
+            raise ValueError("PagedKV: pools must be bfloat16 / float16 / float32 or fp8 "
+                             "(float8_e4m3fn / float8_e5m2) and of one "
                              f"dtype; got {k_pool.dtype} / {v_pool.dtype}")
         npg, H, P, D = k_pool.shape
         if npg < 1 or H < 1 or D < 1 or P < 1 or P > 65536 or P & (P - 1):

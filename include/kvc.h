@@ -41,8 +41,9 @@
  *     same workspace with the same table.
  *   - SELECT of plain-norm rows (KVC_SCORE_NORM) reads the norm region only, and only columns
  *     [0, zone_len) of a row decide its result: the caller may fill those itself (row
- *     layer.row0 + b*heads + h, norm_row_stride elements of dtype apart) and launch SELECT
- *     without SCORE.  Columns from zone_len up to norm_row_stride may hold anything.
+ *     layer.row0 + b*heads + h, norm_row_stride elements of the SCORE dtype apart, norms in that
+ *     dtype: dtype itself, or bf16 for the fp8 dtypes) and launch SELECT without SCORE.
+ *     Columns from zone_len up to norm_row_stride may hold anything.
  *
  * Ownership: the caller allocates outputs and the workspace; the library never allocates,
  * frees or synchronises.  Entry points are reentrant (no global mutable state, no environment
@@ -72,7 +73,25 @@ typedef struct ihipStream_t* kvc_stream_t; /* a hipStream_t; NULL = legacy defau
 /* KVC_F16: IEEE half (what transformers >= 5 loads pythia checkpoints as: dtype="auto").  Its
  * norm follows torch's non-vectorised CPU reduction (one fp32 accumulator in dim order), not the
  * 8-lane order of bf16/fp32 -- see DESIGN.md. */
-enum kvc_dtype { KVC_F32 = 0, KVC_BF16 = 1, KVC_F16 = 2 };
+enum kvc_dtype {
+  KVC_F32 = 0,
+  KVC_BF16 = 1,
+  KVC_F16 = 2,
+  /* fp8 K/V caches, the OCP formats (torch.float8_e4m3fn / float8_e5m2; gfx950's native fp8), with
+   * dequantisation scale 1.  Elements are 1 byte: strides, alignment, spans and GATHER units follow
+   * the D-byte rows.  Every fp8 pattern upcasts to bf16 exactly, and the SCORE dtype of an fp8 call
+   * is bf16: the kept positions, the norm region (norm_row_stride counts 2-byte elements), the
+   * tile statistics, the index region and the workspace layout are those of a bf16 call on
+   * K.to(bf16) -- torch.norm's 8-lane FMA order over the D upcast elements, norms rounded to bf16,
+   * u16 keys, NaN patterns as the one NaN key, e5m2 +-inf giving an inf norm.  GATHER copies the
+   * kept rows' BYTES of K and V verbatim: no NaN rewrite, V is never interpreted.  head_dim is 64,
+   * 128 or 256 (else KVC_E_HEADDIM).  The fnuz formats and raw byte tensors have no code; a
+   * general k_scale is out of scope (scaling then rounding can change ties, and kvc_layer_t has no
+   * room for it in ABI 4).  The kvc_attn_* / kvc_heavy_hitters entries refuse them (KVC_E_DTYPE):
+   * attention tensors are not fp8.  Additive within ABI 4: an older library answers KVC_E_DTYPE. */
+  KVC_F8E4M3 = 16,
+  KVC_F8E5M2 = 17
+};
 /* KVC_ASC keeps the smallest keys (argsort ascending, "keep_low");
  * KVC_DESC keeps the largest (argsort descending / topk largest, "keep_high", snapkv). */
 enum kvc_order { KVC_ASC = 0, KVC_DESC = 1 };
@@ -124,8 +143,10 @@ enum kvc_device_status {
 enum kvc_status {
   KVC_OK = 0,
   KVC_E_ARG = -1,       /* malformed layer table / params                             */
-  KVC_E_DTYPE = -2,     /* dtype is not bf16 / fp16 / fp32                            */
-  KVC_E_HEADDIM = -3,   /* head_dim*elem_size not in {64,128,160,256,320,512,1024} B  */
+  KVC_E_DTYPE = -2,     /* dtype is not bf16 / fp16 / fp32 / fp8 e4m3fn / fp8 e5m2 (the
+                           attention entries: not bf16 / fp16 / fp32)                  */
+  KVC_E_HEADDIM = -3,   /* head_dim*elem_size not in {64,128,160,256,320,512,1024} B;
+                           fp8 dtypes: head_dim not in {64,128,256}                    */
   KVC_E_ALIGN = -4,     /* a base pointer or stride is not 16-byte aligned            */
   KVC_E_TOO_LONG = -5,  /* a scored zone is longer than kvc_max_zone_len() (2^24), or a
                            KVC_ALGO_STABLE selection zone longer than 65 536            */
@@ -145,7 +166,7 @@ typedef struct kvc_layer {
   const void* v;
   void* k_out;
   void* v_out;
-  int64_t k_stride[3]; /* element strides of dims batch, heads, seq */
+  int64_t k_stride[3]; /* element strides of dims batch, heads, seq (fp8: 1-byte elements) */
   int64_t v_stride[3];
   int32_t seq_len;     /* S */
   int32_t zone_start;  /* scored zone [zone_start, zone_start + zone_len) */
@@ -181,7 +202,7 @@ typedef struct kvc_plan_info {
   size_t norm_offset;      /* workspace byte offset of the norm region                    */
   size_t index_offset;     /* workspace byte offset of the int32 index region             */
   size_t workspace_bytes;  /* total workspace the launch needs                              */
-  int64_t norm_row_stride; /* elements (of dtype) per row in the norm region               */
+  int64_t norm_row_stride; /* elements (of the score dtype: dtype, bf16 for fp8) per norm row */
   int64_t index_row_stride;/* int32 entries per row in the index region                   */
   int64_t rows;            /* num_layers * batch * heads                                   */
   int64_t score_tiles;     /* SCORE work items                                             */
