@@ -411,6 +411,53 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
   return KVC_OK;
 }
 
+// kvc_plan_scaled / kvc_launch_scaled (include/kvc.h, "Per-token-scaled fp8 paged caches"):
+// plan_ragged_impl (ragged == nullptr: the single-length paged plan), then the scale description
+// of every layer.  scales == nullptr: plan_ragged_impl alone.
+static int plan_scaled_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
+                            const kvc_ragged_t* ragged, const kvc_scales_t* scales, int nl,
+                            kvc_plan_info_t* info, bool fill) {
+  int rc = plan_ragged_impl(p, layers, pages, ragged, nl, info, fill);
+  if (rc != KVC_OK || !scales) return rc;
+  if (nl > 0 && !pages) return KVC_E_ARG;  // every scaled layer is paged
+  if (!is_fp8(p->dtype)) return KVC_E_DTYPE;
+  constexpr int kKnown =
+      KVC_SCALE_K_UNIFORM | KVC_SCALE_V_UNIFORM | KVC_SCALE_K_NONE | KVC_SCALE_V_NONE;
+  for (int l = 0; l < nl; ++l) {
+    const kvc_scales_t& z = scales[l];
+    const kvc_pages_t& g = pages[l];
+    // a dense output has no channel for the moved scales
+    if (g.in_place != 1 || layers[l].k_out != layers[l].k || layers[l].v_out != layers[l].v)
+      return KVC_E_ARG;
+    if ((z.flags & ~kKnown) || z.reserved != 0 ||
+        ((z.flags & KVC_SCALE_K_UNIFORM) && (z.flags & KVC_SCALE_K_NONE)) ||
+        ((z.flags & KVC_SCALE_V_UNIFORM) && (z.flags & KVC_SCALE_V_NONE)))
+      return KVC_E_ARG;
+    const struct {
+      const float* ptr;
+      int64_t page, head, slot;
+      bool read, pool;
+    } side[2] = {
+        {z.k_scale, z.k_page_stride, z.k_stride[0], z.k_stride[1], !(z.flags & KVC_SCALE_K_NONE),
+         !(z.flags & (KVC_SCALE_K_NONE | KVC_SCALE_K_UNIFORM))},
+        // (a uniform V scale is never read: its pointer may be anything)
+        {z.v_scale, z.v_page_stride, z.v_stride[0], z.v_stride[1],
+         !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM)),
+         !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM))}};
+    for (const auto& s : side) {
+      if (!s.read) continue;
+      if (!s.ptr) return KVC_E_ARG;
+      if ((uintptr_t)s.ptr & 3u) return KVC_E_ALIGN;
+      // a zero stride would make the scales of different rows -- of different heads, each
+      // compacted by its own workgroup -- one word
+      if (s.pool && ((g.num_pages > 1 && s.page == 0) || (p->heads > 1 && s.head == 0) ||
+                     (g.page_size > 1 && s.slot == 0)))
+        return KVC_E_ARG;
+    }
+  }
+  return KVC_OK;
+}
+
 // Every launch goes through hipLaunchKernel, whose return value is this launch's own status (a
 // caller's pending HIP error is neither consumed nor reported as ours).
 template <typename... P, typename... A>
@@ -613,11 +660,14 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
 // layers' destinations (gather_dest_kernel).
 // pages != nullptr (kvc_launch_paged; cn <= kPagedLayers): SCORE and GATHER read K / V through the
 // layers' block tables (kvc_paged.h), SELECT as with dests.
+// scales != nullptr (kvc_launch_scaled; fp8, paged, in place): SCORE and GATHER are the scaled
+// instances, which also read / move the layers' scale words.
 template <int DT, int NC>
 static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, const kvc_layer_t* layers,
                         int nl, int c0, int cn, char* w, hipStream_t s,
                         const kvc_dest_t* dests = nullptr,
-                        const kvc_pages_t* pages = nullptr) {
+                        const kvc_pages_t* pages = nullptr,
+                        const kvc_scales_t* scales = nullptr) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
   constexpr int SDT = score_dt(DT);  // the selection's runtime dtype (bf16 for fp8 rows)
@@ -656,7 +706,22 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
   int rc = KVC_OK;
   PagesChunk PC;  // filled for paged launches only
   if (pages) fill_pages_chunk(&PC, p, layers + c0, pages + c0, dests ? dests + c0 : nullptr, cn);
-  if ((p->phases & KVC_PHASE_SCORE) && tile_end > tile_base && !ext)
+  ScalesChunk ZC;  // filled for scaled launches only
+  if (scales) {
+    memset(&ZC, 0, sizeof(ZC));
+    memcpy(ZC.s, scales + c0, (size_t)cn * sizeof(kvc_scales_t));
+  }
+  if constexpr (is_fp8(DT)) {
+    if (scales && (p->phases & KVC_PHASE_SCORE) && tile_end > tile_base && !ext) {
+      constexpr int per_wg = score_waves(NC);
+      const int64_t chunk_tiles = tile_end - tile_base;
+      rc = launch_k(score_paged_scaled_kernel<DT, NC>,
+                    dim3((unsigned)((chunk_tiles + per_wg - 1) / per_wg)), dim3(per_wg * 64), 0, s,
+                    PC, ZC, cn, H, tile_base, chunk_tiles, norms, nstride, tmax, nstride / kTile,
+                    status);
+    }
+  }
+  if ((p->phases & KVC_PHASE_SCORE) && tile_end > tile_base && !ext && !scales)
     rc = pages ? launch_score_paged<DT, NC>(PC, cn, H, tile_base, tile_end - tile_base, norms,
                                             nstride, tmax, status, s)
                : launch_score<DT, NC>(T, cn, H, tile_base, tile_end - tile_base, norms, nstride,
@@ -712,6 +777,12 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                            long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if constexpr (is_fp8(DT)) {
+    if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && scales)  // every layer in place
+      return launch_k(gather_paged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
+                      dim3(kGatherThreads), 0, s, PC, ZC, H, BH, static_cast<const int32_t*>(idx),
+                      istride, (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status);
+  }
   if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && pages)
     return launch_gather_paged<DT, NC>(PC, cn, H, BH, idx, istride,
                                        (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
@@ -772,7 +843,7 @@ template <int DT, int NC>
 static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& info,
                                const kvc_layer_t* layers, const kvc_pages_t* pages,
                                const kvc_ragged_t* ragged, int nl, int c0, int cn, char* w,
-                               hipStream_t s) {
+                               hipStream_t s, const kvc_scales_t* scales = nullptr) {
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
   const int H = p->heads, BH = p->batch * p->heads;
   char* norms = w + info.norm_offset;
@@ -783,6 +854,11 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
   memcpy(C.l, layers + c0, (size_t)cn * sizeof(kvc_layer_t));
   memcpy(C.p, pages + c0, (size_t)cn * sizeof(kvc_pages_t));
   for (int l = 0; l < cn; ++l) C.s[l] = ragged[c0 + l].dev;
+  ScalesChunk ZC;  // filled for scaled launches only (fp8: plan_scaled_impl)
+  if (scales) {
+    memset(&ZC, 0, sizeof(ZC));
+    memcpy(ZC.s, scales + c0, (size_t)cn * sizeof(kvc_scales_t));
+  }
   const int64_t tile_base = layers[c0].tile0;
   const int64_t tile_end = c0 + cn < nl ? (int64_t)layers[c0 + cn].tile0 : info.score_tiles;
   bool sel = false, long_zone = false, snap = false;
@@ -801,10 +877,18 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
     for (int l = c0; l < c0 + cn; ++l)
       if (layer_selects(layers[l]) && layers[l].zone_len > zmax) zmax = layers[l].zone_len;
     const int64_t per_block = (int64_t)kRaggedTiles * kTile;
-    rc = launch_k(score_ragged_kernel<DT, NC>,
-                  dim3((unsigned)(cn * BH), (unsigned)((zmax + per_block - 1) / per_block)),
-                  dim3(score_waves(NC) * 64), 0, s, C, H, BH, norms, nstride, tmax,
-                  nstride / kTile, status);
+    const dim3 grid((unsigned)(cn * BH), (unsigned)((zmax + per_block - 1) / per_block));
+    bool done = false;
+    if constexpr (is_fp8(DT)) {
+      if (scales) {
+        rc = launch_k(score_ragged_scaled_kernel<DT, NC>, grid, dim3(score_waves(NC) * 64), 0, s,
+                      C, ZC, H, BH, norms, nstride, tmax, nstride / kTile, status);
+        done = true;
+      }
+    }
+    if (!done)
+      rc = launch_k(score_ragged_kernel<DT, NC>, grid, dim3(score_waves(NC) * 64), 0, s, C, H, BH,
+                    norms, nstride, tmax, nstride / kTile, status);
   }
   if (rc != KVC_OK) return rc;
   if ((p->phases & KVC_PHASE_SELECT) && sel) {
@@ -813,6 +897,12 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
                                   istride, long_zone, scratch, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if constexpr (is_fp8(DT)) {
+    if ((p->phases & KVC_PHASE_GATHER) && max_out > 0 && scales)
+      return launch_k(gather_ragged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
+                      dim3(kGatherThreads), 0, s, C, ZC, H, BH, static_cast<const int32_t*>(idx),
+                      istride, status);
+  }
   if ((p->phases & KVC_PHASE_GATHER) && max_out > 0)
     rc = launch_k(gather_ragged_kernel<DT, NC>, dim3((unsigned)(cn * BH)), dim3(kGatherThreads), 0,
                   s, C, H, BH, static_cast<const int32_t*>(idx), istride, status);
@@ -1101,6 +1191,41 @@ int kvc_launch_ragged(const kvc_params_t* p, const kvc_layer_t* layers, const kv
       return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
         return launch_chunk_ragged<decltype(dt)::value, decltype(ncv)::value>(
             p, info, layers, pages, ragged, nl, c0, cn, w, s);
+      });
+    });
+  }
+  return rc;
+}
+
+int kvc_plan_scaled(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, const kvc_scales_t* scales, int num_layers,
+                    kvc_plan_info_t* info) {
+  return kvc::plan_scaled_impl(params, layers, pages, ragged, scales, num_layers, info, true);
+}
+
+int kvc_launch_scaled(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
+                      const kvc_ragged_t* ragged, const kvc_scales_t* scales, int nl, void* ws,
+                      size_t ws_bytes, kvc_stream_t stream) {
+  using namespace kvc;
+  if (!scales) return kvc_launch_ragged(p, layers, pages, ragged, nl, ws, ws_bytes, stream);
+  kvc_plan_info_t info;
+  int rc = plan_scaled_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, scales, nl, &info,
+                            false);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0) return KVC_OK;
+  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  const int nc = p->head_dim * esize(p->dtype) / 16;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kPagedLayers) {
+    const int cn = nl - c0 < kPagedLayers ? nl - c0 : kPagedLayers;
+    rc = with_kv_dtype(p->dtype, [&](auto dt) {
+      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
+        constexpr int DT = decltype(dt)::value, NC = decltype(ncv)::value;
+        if (ragged)
+          return launch_chunk_ragged<DT, NC>(p, info, layers, pages, ragged, nl, c0, cn, w, s,
+                                             scales);
+        return launch_chunk<DT, NC>(p, info, layers, nl, c0, cn, w, s, nullptr, pages, scales);
       });
     });
   }

@@ -77,7 +77,19 @@ struct EitherRows {
 // The proof speaks about ROWS: from memory it needs only that different rows of one (b, h)
 // sequence are different bytes (the layouts' own paragraphs: non-zero strides here, kvc_paged.h).
 // Sink rows have src == dst and are not touched.  Rows [n_out, S) are never written.
-template <int DT, int NC, typename Src, typename Dst>
+//
+// SC (per-token-scaled fp8 paged caches, include/kvc.h; Src and Dst give page_of() /
+// scales_at()): a row's K and V scale words are PART OF THE ROW.  Thread j of the workgroup loads
+// the two words of the source row src(t) of pass row t = t0 + j, as uint32, among the loads of the
+// pass -- before its s_waitcnt vmcnt(0) and the barrier -- and stores them to the slots of row t
+// after it.  So every step of the proof above reads unchanged with "row" meaning a row's D bytes
+// of K, of V and its two scale words: the scale slot of row t is only ever overwritten by the
+// pass that writes row t, whose loads -- of any wave, scale words included -- have returned; and
+// distinct rows have distinct scale slots (kvc_plan_scaled: non-zero scale strides on every dim
+// larger than 1, the table's distinct page ids).  A side whose scale is uniform or absent
+// (nullptr from scales_at) moves nothing.  A dropped row store (bad destination page id) drops
+// its scale stores with it.  All of it is behind `if constexpr (SC)`.
+template <int DT, int NC, bool SC = false, typename Src, typename Dst>
 __device__ __forceinline__ void gather_passes(const kvc_layer_t* ly, int r, int H, bool inplace,
                                               const Src& src, const Dst& dst,
                                               const int32_t* __restrict__ gidx,
@@ -107,6 +119,16 @@ __device__ __forceinline__ void gather_passes(const kvc_layer_t* ly, int r, int 
   for (int t0 = t_begin; t0 < t_end; t0 += ROWS) {  // ascending passes
     const int nu = min(ROWS, t_end - t0) * NC;
     uint4 xk[kDestIters], xv[kDestIters];
+    // SC: thread j < rows of the pass carries the two scale words of pass row j (its own index
+    // and page lookups: two live registers per thread instead of two per unit, which keeps the
+    // scaled instances at their twins' occupancy).  The row's units report a bad index or page id.
+    // Its three dependent loads ride beside the units' own: the index with their indices, the
+    // page id before their lookups, the scale words behind their K / V loads -- as a chain of its
+    // own in front of them it cost the pass three more memory latencies.
+    [[maybe_unused]] uint32_t wk = 0, wv = 0;
+    [[maybe_unused]] const int trow = t0 + (int)threadIdx.x;
+    [[maybe_unused]] const bool has_row = (int)threadIdx.x < ROWS && trow < t_end;
+    [[maybe_unused]] int srow = trow, spage = 0;  // the row's source row and its clamped page id
     bool gat[kDestIters];
     int zi[kDestIters];
     // the index loads of all units are issued first.  (The compiler still waits for each unit's
@@ -118,6 +140,16 @@ __device__ __forceinline__ void gather_passes(const kvc_layer_t* ly, int r, int 
       const int t = t0 + u / NC;
       gat[i] = u < nu && t >= sink && t < sink + nsel;
       zi[i] = gat[i] ? irow[t - sink] : 0;
+    }
+    if constexpr (SC) {
+      static_assert(ROWS <= kGatherThreads, "one thread per row of a pass");
+      if (has_row) {
+        if (trow >= sink && trow < sink + nsel)
+          srow = zone_start + min(max(irow[trow - sink], 0), zone_len - 1);
+        else if (trow >= sink)
+          srow = tail_start + (trow - sink - nsel);
+        spage = src.page_of(srow);
+      }
     }
 #pragma unroll
     for (int i = 0; i < kDestIters; ++i) {
@@ -138,10 +170,31 @@ __device__ __forceinline__ void gather_passes(const kvc_layer_t* ly, int r, int 
         xv[i] = *reinterpret_cast<const uint4*>(vs + c * 16);
       }
     }
+    if constexpr (SC) {
+      if (has_row) {
+        uint32_t* sk;
+        uint32_t* sv;
+        src.scales_at(spage, srow, &sk, &sv);
+        if (sk) wk = *sk;
+        if (sv) wv = *sv;
+      }
+    }
     if (inplace) {  // uniform over the workgroup
       // every load of this pass has returned in this wave, then in all waves, before any store
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
+    }
+    if constexpr (SC) {
+      if (has_row) {
+        uint32_t* sk;
+        uint32_t* sv;
+        bool ok;
+        dst.scales_at(dst.page_of(trow, &ok), trow, &sk, &sv);
+        if (ok) {  // dropped with the row's stores otherwise
+          if (sk) __builtin_nontemporal_store(wk, sk);
+          if (sv) __builtin_nontemporal_store(wv, sv);
+        }
+      }
     }
 #pragma unroll
     for (int i = 0; i < kDestIters; ++i) {

@@ -53,11 +53,19 @@ struct PageRow {
 // CP = 10 instances 36-77 more instructions, and a reordered score_kernel is all the dense side
 // gains.  A fix to one tile is a fix to both.
 // ---------------------------------------------------------------------------------------------
-template <int DT, int NC>
+//
+// SC (per-token-scaled fp8 caches, include/kvc.h): the lane that owns token `lane` of the tile
+// loads that token's K scale -- through one more lookup of the same clamped page id, issued before
+// the phases so that the load is in flight behind the key loads -- or the layer's one uniform
+// float, and the stored norm is bf16(r * |s|): ONE fp32 multiply between the sqrt and the bf16
+// rounding.  The tile maximum is taken from those bits.  Every SC line is behind `if constexpr`:
+// the unscaled instances compile from the code they had.
+template <int DT, int NC, bool SC = false>
 __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kvc_pages_t* pg,
                                                  int row, int tt, int H, char* wl, char* norms,
                                                  int64_t norm_stride, uint32_t* tmax,
-                                                 int64_t tmax_stride, uint32_t* status) {
+                                                 int64_t tmax_stride, uint32_t* status,
+                                                 const kvc_scales_t* sc = nullptr) {
   constexpr int ESZ = DTypeTraits<DT>::esz;
   constexpr int SDT = score_dt(DT);  // the norm region's dtype (bf16 for fp8 keys)
   constexpr int CP = score_cp(NC);
@@ -85,6 +93,21 @@ __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kv
       const int id = pr.page(s, &ok);
       bad |= !ok;
       rowp[it] = base + (int64_t)id * pbytes + (int64_t)(s & pr.mask) * sbytes;
+    }
+  }
+  float kscale = 1.0f;  // SC: this lane's token's scale (1: KVC_SCALE_K_NONE, lanes past the zone)
+  if constexpr (SC) {
+    if (sc->flags & KVC_SCALE_K_UNIFORM) {
+      kscale = *sc->k_scale;
+    } else if (!(sc->flags & KVC_SCALE_K_NONE) && lane < ntok) {
+      const int s = s0 + lane;
+      bool ok;
+      const int64_t id = pr.page(s, &ok);
+      bad |= !ok;
+      // (a plain load: in a pool stored [N, P, H] the heads' scales of a token share a cache
+      // line, which the waves of the other heads come for)
+      kscale = sc->k_scale[id * sc->k_page_stride + (int64_t)h * sc->k_stride[0] +
+                           (int64_t)(s & pr.mask) * sc->k_stride[1]];
     }
   }
   if (bad && status) atomicOr(status, (uint32_t)KVC_DEV_INDEX_RANGE);
@@ -124,7 +147,8 @@ __device__ __forceinline__ void score_paged_tile(const kvc_layer_t* ly, const kv
     float s = acc[0];
 #pragma unroll
     for (int j = 1; j < 8; ++j) s = s + acc[j];
-    const float r = __builtin_sqrtf(s);
+    float r = __builtin_sqrtf(s);
+    if constexpr (SC) r = r * __builtin_fabsf(kscale);
     char* nrow = norms + (int64_t)(ly->row0 + row) * norm_stride * DTypeTraits<SDT>::esz;
     if constexpr (DT != KVC_F32) {
       bits = bits16_dt<SDT>(r);
@@ -156,6 +180,35 @@ __global__ void __launch_bounds__(score_waves(NC) * 64)
     const TileAt at = locate_tile(T.l, nl, tile_base + gl);
     score_paged_tile<DT, NC>(T.l + at.layer, T.p + at.layer, at.row, at.tile, H, lds[wid], norms,
                              norm_stride, tmax, tmax_stride, status);
+  }
+}
+
+// The scale descriptions of a chunk's layers travel by value beside its PagesChunk / RaggedChunk
+// (2.25 KiB: 9.75 KiB of kernel arguments with a PagesChunk, below the 12.2 KiB known to launch).
+struct ScalesChunk {
+  kvc_scales_t s[kPagedLayers];
+};
+
+// score_paged_kernel for scaled fp8 layers: the same grid-stride loop over score_paged_tile<SC>.
+// A kernel of its own name, so that score_paged_kernel's instances stay what they were; the loop
+// is a copy for the same reason (kvc_ragged.h, score_ragged_scaled_kernel: a shared body changed
+// the existing instances' code).
+template <int DT, int NC>
+__global__ void __launch_bounds__(score_waves(NC) * 64)
+    score_paged_scaled_kernel(const PagesChunk T, const ScalesChunk Z, int nl, int H,
+                              int64_t tile_base, int64_t chunk_tiles, char* __restrict__ norms,
+                              int64_t norm_stride, uint32_t* __restrict__ tmax,
+                              int64_t tmax_stride, uint32_t* status) {
+  constexpr int CP = score_cp(NC);
+  constexpr int ROWB = score_rowb(CP);
+  constexpr int kScoreWaves = score_waves(NC);
+  __shared__ __attribute__((aligned(16))) char lds[kScoreWaves][kTile * ROWB];
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * kScoreWaves;
+  for (int64_t gl = (int64_t)blockIdx.x * kScoreWaves + wid; gl < chunk_tiles; gl += stride) {
+    const TileAt at = locate_tile(T.l, nl, tile_base + gl);
+    score_paged_tile<DT, NC, true>(T.l + at.layer, T.p + at.layer, at.row, at.tile, H, lds[wid],
+                                   norms, norm_stride, tmax, tmax_stride, status, Z.s + at.layer);
   }
 }
 
@@ -210,6 +263,58 @@ struct PagedRows {
     return ok;
   }
 };
+
+// PagedRows of a scaled layer: page_of() / scales_at() give the addresses of a row's K and V
+// scale words through the page id that locate() gives its K and V bytes through -- nullptr for a
+// side whose scale is uniform or absent (nothing of it moves).
+struct ScaledPagedRows : PagedRows {
+  uint32_t* ksb;
+  uint32_t* vsb;
+  int64_t ksp, kss1, vsp, vss1;
+  __device__ __forceinline__ ScaledPagedRows(int esz, const kvc_layer_t* ly, const kvc_pages_t* pg,
+                                             const kvc_scales_t* sc, int b, int h)
+      : PagedRows(esz, ly, pg, b, h),
+        ksb((sc->flags & (KVC_SCALE_K_UNIFORM | KVC_SCALE_K_NONE))
+                ? nullptr
+                : reinterpret_cast<uint32_t*>(sc->k_scale) + (int64_t)h * sc->k_stride[0]),
+        vsb((sc->flags & (KVC_SCALE_V_UNIFORM | KVC_SCALE_V_NONE))
+                ? nullptr
+                : reinterpret_cast<uint32_t*>(sc->v_scale) + (int64_t)h * sc->v_stride[0]),
+        ksp(sc->k_page_stride),
+        kss1(sc->k_stride[1]),
+        vsp(sc->v_page_stride),
+        vss1(sc->v_stride[1]) {}
+  // the clamped page id of logical row s, as locate() looks it up (*ok: it was in range)
+  __device__ __forceinline__ int page_of(int s, bool* ok = nullptr) const {
+    bool in_range;
+    const int id = pr.page(s, &in_range);
+    if (ok) *ok = in_range;
+    return id;
+  }
+  // addresses of the scale words of logical row s, which lives in page `id`
+  __device__ __forceinline__ void scales_at(int64_t id, int s, uint32_t** sk,
+                                            uint32_t** sv) const {
+    const int slot = s & pr.mask;
+    *sk = ksb ? ksb + id * ksp + slot * kss1 : nullptr;
+    *sv = vsb ? vsb + id * vsp + slot * vss1 : nullptr;
+  }
+};
+
+// gather_paged_kernel for scaled fp8 layers (always in place: kvc_plan_scaled): gather_passes<SC>
+// over ScaledPagedRows.  A kernel of its own name, as score_paged_scaled_kernel.
+template <int DT, int NC>
+__global__ void __launch_bounds__(kGatherThreads, 8)
+    gather_paged_scaled_kernel(const PagesChunk T, const ScalesChunk Z, int H, int BH,
+                               const int32_t* __restrict__ gidx, int64_t idx_stride, int shared,
+                               uint32_t* status) {
+  const int li = (int)blockIdx.x / BH;
+  const kvc_layer_t* ly = T.l + li;
+  const int r = (int)blockIdx.x - li * BH;
+  const int b = r / H, h = r - (r / H) * H;
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  const ScaledPagedRows rows(ESZ, ly, T.p + li, Z.s + li, b, h);
+  gather_passes<DT, NC, true>(ly, r, H, true, rows, rows, gidx, idx_stride, shared, status);
+}
 
 template <int DT, int NC>
 __global__ void __launch_bounds__(kGatherThreads)

@@ -88,6 +88,37 @@ __global__ void __launch_bounds__(score_waves(NC) * 64)
                              tmax_stride, status);
 }
 
+// score_ragged_kernel for scaled fp8 layers (score_paged_tile<SC>), under a name of its own.  Its
+// prologue is a COPY of score_ragged_kernel's, deliberately: as one __device__ body over the SC
+// flag, called from two thin kernels, 47 of the existing score_paged_kernel / score_ragged_kernel
+// instances compile to other code than before (tools/isa_diff.py: an instruction and an SGPR here
+// and there), and the existing instances are to stay what they were.  A fix to one prologue is a
+// fix to both.
+template <int DT, int NC>
+__global__ void __launch_bounds__(score_waves(NC) * 64)
+    score_ragged_scaled_kernel(const RaggedChunk T, const ScalesChunk Z, int H, int BH,
+                               char* __restrict__ norms, int64_t norm_stride,
+                               uint32_t* __restrict__ tmax, int64_t tmax_stride,
+                               uint32_t* status) {
+  constexpr int CP = score_cp(NC);
+  constexpr int ROWB = score_rowb(CP);
+  constexpr int kScoreWaves = score_waves(NC);
+  __shared__ __attribute__((aligned(16))) char lds[kScoreWaves][kTile * ROWB];
+  const int li = (int)blockIdx.x / BH, r = (int)blockIdx.x - li * BH;
+  const kvc_seq_t q = load_seq(T.s[li] + r / H);
+  if (!(q.n_select > 0 && q.n_select < q.zone_len)) return;
+  // (never past the planned norm row, whatever a rewritten record says)
+  const int ntile = min((q.zone_len + kTile - 1) / kTile, (int)tmax_stride);
+  const int t0 = (int)blockIdx.y * kRaggedTiles;
+  if (t0 >= ntile) return;
+  const int t1 = min(ntile, t0 + kRaggedTiles);
+  const kvc_layer_t y = seq_layer(T.l + li, q);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int tt = t0 + wid; tt < t1; tt += kScoreWaves)
+    score_paged_tile<DT, NC, true>(&y, T.p + li, r, tt, H, lds[wid], norms, norm_stride, tmax,
+                                   tmax_stride, status, Z.s + li);
+}
+
 // SELECT: the workgroups of select_kernel / select_global_kernel / select_long_kernel, one per
 // (layer, b, h) row of the envelope's row numbering, with zone_len, n_select, score_mode and
 // pool_kernel of the row's record.  n_cap is the launch's capacity (the envelope's zone): a
@@ -176,6 +207,23 @@ __global__ void __launch_bounds__(kGatherThreads)
   constexpr int ESZ = DTypeTraits<DT>::esz;
   const PagedRows rows(ESZ, &y, T.p + li, b, h);
   gather_passes<DT, NC>(&y, r, H, true, rows, rows, gidx, idx_stride, 0, status);
+}
+
+// gather_ragged_kernel for scaled fp8 layers: the rows' scale words move with them
+// (gather_passes<SC> over ScaledPagedRows), under a name of its own.
+template <int DT, int NC>
+__global__ void __launch_bounds__(kGatherThreads, 8)
+    gather_ragged_scaled_kernel(const RaggedChunk T, const ScalesChunk Z, int H, int BH,
+                                const int32_t* __restrict__ gidx, int64_t idx_stride,
+                                uint32_t* status) {
+  const int li = (int)blockIdx.x / BH, r = (int)blockIdx.x - li * BH;
+  const int b = r / H, h = r - (r / H) * H;
+  const kvc_seq_t q = load_seq(T.s[li] + b);
+  if (q.n_out <= q.sink_len) return;
+  const kvc_layer_t y = seq_layer(T.l + li, q);
+  constexpr int ESZ = DTypeTraits<DT>::esz;
+  const ScaledPagedRows rows(ESZ, &y, T.p + li, Z.s + li, b, h);
+  gather_passes<DT, NC, true>(&y, r, H, true, rows, rows, gidx, idx_stride, 0, status);
 }
 
 }  // namespace kvc

@@ -306,10 +306,13 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None):
+def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None, scales=None):
     """Plan one table and allocate its workspace.  The table itself travels in the kernels'
     arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    if ragged is not None:
+    if scales is not None:  # scaled fp8 paged layers, compacted in place (ragged or not)
+        rc, info = N.plan_scaled(params, table, pages, ragged, scales)
+        N.check(rc, "kvc_plan_scaled")
+    elif ragged is not None:
         rc, info = N.plan_ragged(params, table, pages, ragged)
         N.check(rc, "kvc_plan_ragged")
     elif pages is not None:
@@ -333,7 +336,8 @@ def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None
     return ws, info
 
 
-def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, ragged=None):
+def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, ragged=None,
+            scales=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
@@ -344,7 +348,10 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, rag
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        if ragged is not None:
+        if scales is not None:
+            rc = N.launch_scaled(params, table, pages, ragged, scales, ws.data_ptr(),
+                                 int(info.workspace_bytes), stream.cuda_stream)
+        elif ragged is not None:
             rc = N.launch_ragged(params, table, pages, ragged, ws.data_ptr(),
                                  int(info.workspace_bytes), stream.cuda_stream)
         elif pages is not None:
@@ -358,7 +365,8 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, rag
                                stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch_ragged" if ragged is not None else
+        N.check(rc, "kvc_launch_scaled" if scales is not None else
+                "kvc_launch_ragged" if ragged is not None else
                 "kvc_launch_paged" if pages is not None else
                 "kvc_launch" if dests is None else "kvc_launch_dest")
         if _timer is not None:

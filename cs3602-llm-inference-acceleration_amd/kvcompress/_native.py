@@ -69,6 +69,14 @@ assert SEQ_DTYPE.itemsize == 48
 RAGGED_DTYPE = np.dtype([("host", "<u8"), ("dev", "<u8")])
 assert RAGGED_DTYPE.itemsize == 16
 
+# struct kvc_scales (include/kvc.h: per-token-scaled fp8 paged caches) -- 72 bytes
+SCALES_DTYPE = np.dtype([
+    ("k_scale", "<u8"), ("v_scale", "<u8"), ("k_page_stride", "<i8"), ("v_page_stride", "<i8"),
+    ("k_stride", "<i8", (2,)), ("v_stride", "<i8", (2,)), ("flags", "<i4"), ("reserved", "<i4"),
+])
+assert SCALES_DTYPE.itemsize == 72
+SCALE_K_UNIFORM, SCALE_V_UNIFORM, SCALE_K_NONE, SCALE_V_NONE = 1, 2, 4, 8  # enum kvc_scale_flag
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -108,7 +116,8 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_source_digest",
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
            "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
-           "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged")
+           "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged",
+           "kvc_plan_scaled", "kvc_launch_scaled")
 
 _lib = None
 
@@ -161,6 +170,13 @@ def lib():
                                       ctypes.POINTER(PlanInfo)]
         L.kvc_launch_ragged.restype = i32
         L.kvc_launch_ragged.argtypes = [ctypes.POINTER(Params), vp, vp, vp, i32, vp,
+                                        ctypes.c_size_t, vp]
+    if hasattr(L, "kvc_plan_scaled"):  # additive within ABI 4, like the ragged entries
+        L.kvc_plan_scaled.restype = i32
+        L.kvc_plan_scaled.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, i32,
+                                      ctypes.POINTER(PlanInfo)]
+        L.kvc_launch_scaled.restype = i32
+        L.kvc_launch_scaled.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, i32, vp,
                                         ctypes.c_size_t, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
@@ -288,6 +304,35 @@ def launch_ragged(params, table, pages, ragged, ws_ptr, ws_bytes, stream_ptr):
     return lib().kvc_launch_ragged(ctypes.byref(params), table.ctypes.data,
                                    _opt(pages, PAGES_DTYPE, len(table)),
                                    _opt(ragged, RAGGED_DTYPE, len(table)), len(table), ws_ptr,
+                                   ws_bytes, stream_ptr)
+
+
+def _need_scaled_entries():
+    if not hasattr(lib(), "kvc_plan_scaled"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_plan_scaled / kvc_launch_scaled (built "
+                                 "before scaled fp8 caches); they need the current library")
+
+
+def plan_scaled(params, table, pages, ragged, scales):
+    """kvc_plan_scaled: `scales` is a SCALES_DTYPE array, one entry per layer, or None (=
+    kvc_plan_ragged); `ragged` None plans the single-length paged call."""
+    info = PlanInfo()
+    _need_scaled_entries()
+    rc = lib().kvc_plan_scaled(ctypes.byref(params), table.ctypes.data,
+                               _opt(pages, PAGES_DTYPE, len(table)),
+                               _opt(ragged, RAGGED_DTYPE, len(table)),
+                               _opt(scales, SCALES_DTYPE, len(table)), len(table),
+                               ctypes.byref(info))
+    return rc, info
+
+
+def launch_scaled(params, table, pages, ragged, scales, ws_ptr, ws_bytes, stream_ptr):
+    """kvc_launch_scaled (scales None = kvc_launch_ragged)."""
+    _need_scaled_entries()
+    return lib().kvc_launch_scaled(ctypes.byref(params), table.ctypes.data,
+                                   _opt(pages, PAGES_DTYPE, len(table)),
+                                   _opt(ragged, RAGGED_DTYPE, len(table)),
+                                   _opt(scales, SCALES_DTYPE, len(table)), len(table), ws_ptr,
                                    ws_bytes, stream_ptr)
 
 

@@ -36,8 +36,22 @@ class PagedKV:
     is host Python): a device tensor is refused rather than silently synchronised on.  `seq_len`
     then reads back as the tuple of lengths, `seq_lens` is that tuple for either kind of layer,
     and `shape` is [B, H, max(seq_lens), D]: the envelope of the B sequences, of which sequence b
-    fills rows [0, seq_lens[b])."""
-    __slots__ = ("k_pool", "v_pool", "block_table", "seq_len", "seq_lens")
+    fills rows [0, seq_lens[b]).
+
+    A per-token quantised fp8 cache gives its dequantisation scales as `k_scale` / `v_scale`:
+    float32 tensors on the pools' device, either a `[num_pages, H, page_size]` view of any
+    non-zero strides addressed by the same block table (a pool stored [N, P, H] is
+    `scales.permute(0, 2, 1)`), or ONE element -- a scale that is the same for every token
+    (vLLM's per-tensor k_scale; read on the device, never synchronised on).  Keys are then ranked
+    by bf16(norm(K8) * |k_scale|) and the scales of the kept rows move with them (include/kvc.h,
+    "Per-token-scaled fp8 paged caches").  A uniform scale changes a result only through rounding
+    ties; a uniform or absent v_scale is ignored.  Scaled layers are compacted in place only.
+    A scale tensor of exactly one element counts as uniform whatever its shape -- a
+    [1, 1, 1] pool of a one-page, one-head, one-slot cache included: it has one row, whose scale
+    need not move.  That the scale pools alias neither each other, nor the K / V pools, nor the
+    pools of another layer of the call is the caller's promise: compress_paged's check that no
+    two in-place layers share a K / V pool does not look at the scale pools."""
+    __slots__ = ("k_pool", "v_pool", "block_table", "seq_len", "seq_lens", "k_scale", "v_scale")
 
     @staticmethod
     def _lengths(seq_len):
@@ -70,7 +84,28 @@ class PagedKV:
                                  f"{x!r}")
         return tuple(int(x) for x in vals)
 
-    def __init__(self, k_pool, v_pool, block_table, seq_len):
+    @staticmethod
+    def _check_scale(name, t, k_pool):
+        """A scale tensor against its pools (device and pointer checks: _check_scale_device)."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"PagedKV: {name} must be a tensor, got {type(t).__name__}")
+        if not E.is_fp8(k_pool.dtype):
+            raise TypeError(f"PagedKV: {name} given with {k_pool.dtype} pools: dequantisation "
+                            "scales belong to fp8 (float8_e4m3fn / float8_e5m2) pools")
+        if t.dtype != torch.float32:
+            raise TypeError(f"PagedKV: {name} must be float32, got {t.dtype}")
+        if t.numel() == 1:
+            return
+        npg, H, P, _ = k_pool.shape
+        if tuple(t.shape) != (npg, H, P):
+            raise ValueError(f"PagedKV: {name} must have one element or be [num_pages, H, "
+                             f"page_size] = {(npg, H, P)}; got {tuple(t.shape)}")
+        if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
+            raise ValueError(f"PagedKV: {name} has stride 0 on a dim larger than 1 (a scale "
+                             f"shared by several rows cannot follow one of them); strides "
+                             f"{tuple(t.stride())}")
+
+    def __init__(self, k_pool, v_pool, block_table, seq_len, k_scale=None, v_scale=None):
         for name, t in (("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"PagedKV: {name} must be a tensor, got {type(t).__name__}")
@@ -85,6 +120,9 @@ class PagedKV:
         if npg < 1 or H < 1 or D < 1 or P < 1 or P > 65536 or P & (P - 1):
             raise ValueError(f"PagedKV: page_size must be a power of two in [1, 65536] and the "
                              f"pool non-empty; got pools of shape {tuple(k_pool.shape)}")
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t is not None:
+                self._check_scale(name, t, k_pool)
         lens = self._lengths(seq_len)
         if lens is None and (isinstance(seq_len, bool) or not isinstance(seq_len, int) or
                              seq_len < 0):
@@ -121,7 +159,16 @@ class PagedKV:
             if t.data_ptr() % 16:
                 raise ValueError(f"PagedKV: {name} pointer not 16-byte aligned (a pool is never "
                                  "copied)")
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t is None:
+                continue
+            if t.device != k_pool.device:
+                raise ValueError(f"PagedKV: {name} is on {t.device}, the pools on "
+                                 f"{k_pool.device}")
+            if t.data_ptr() % 4:
+                raise ValueError(f"PagedKV: {name} pointer not 4-byte aligned")
         self.k_pool, self.v_pool, self.block_table = k_pool, v_pool, block_table
+        self.k_scale, self.v_scale = k_scale, v_scale
         self.seq_len = seq_len if lens is None else lens
         self.seq_lens = (seq_len,) * block_table.size(0) if lens is None else lens
 
@@ -140,6 +187,52 @@ class PagedKV:
     @property
     def page_size(self):
         return self.k_pool.size(2)
+
+    @property
+    def scaled(self):
+        """True when the layer carries a K or a V scale."""
+        return self.k_scale is not None or self.v_scale is not None
+
+    def scales_row(self):
+        """The layer's kvc_scales_t (a SCALES_DTYPE record)."""
+        r = np.zeros(1, dtype=N.SCALES_DTYPE)[0]
+        flags = 0
+        for side, t, uni, none in (("k", self.k_scale, N.SCALE_K_UNIFORM, N.SCALE_K_NONE),
+                                   ("v", self.v_scale, N.SCALE_V_UNIFORM, N.SCALE_V_NONE)):
+            if t is None:
+                flags |= none
+                continue
+            r[side + "_scale"] = t.data_ptr()
+            if t.numel() == 1:
+                flags |= uni
+            else:
+                r[side + "_page_stride"] = t.stride(0)
+                r[side + "_stride"] = (t.stride(1), t.stride(2))
+        r["flags"] = flags
+        return r
+
+    def scales_to_dense(self, n=None, b=None):
+        """(K scales, V scales) [B, H, n] of the first n logical rows, by torch indexing, as
+        to_dense gives the rows; a uniform scale is expanded, a missing one is None."""
+        if n is None:
+            if b is None and self.ragged:
+                raise ValueError("PagedKV.scales_to_dense: a ragged layer needs b (one sequence) "
+                                 "or n")
+            n = self.seq_len if b is None else self.seq_lens[b]
+        table = self.block_table if b is None else self.block_table[b:b + 1]
+        pos = torch.arange(n, device=self.k_pool.device)
+        pg = table[:, :max(-(-n // self.page_size), 1)].long()
+        pg = pg[:, pos // self.page_size]
+        slot = pos % self.page_size
+        H = self.k_pool.size(1)
+
+        def dense(t):
+            if t is None:
+                return None
+            if t.numel() == 1:
+                return t.reshape(1, 1, 1).expand(table.size(0), H, n)
+            return t[pg, :, slot].permute(0, 2, 1)
+        return dense(self.k_scale), dense(self.v_scale)
 
     def to_dense(self, n=None, b=None):
         """(K, V) [B, H, n, D] of the first n (default seq_len) logical rows, by torch indexing:
@@ -239,10 +332,17 @@ def _compress_paged(method, layers, out, kwargs):
     else:
         raise TypeError(f"out must be \"inplace\" or a list, got {type(out).__name__}")
     if any(pk.ragged for pk in layers):
+        if any(d != "inplace" and pk.scaled for pk, d in zip(layers, dests)):
+            raise TypeError("compress_paged: a scaled layer (k_scale / v_scale) is compacted in "
+                            "place only")
         return _compress_ragged(fn, layers, dests, kwargs)
     kvl = [_stand_in(pk) for pk in layers]
     seen = {}
     for i, (pk, (k, v), d) in enumerate(zip(layers, kvl, dests)):  # before anything is enqueued
+        if d != "inplace" and pk.scaled:
+            raise TypeError(f"layer {i}: a scaled layer (k_scale / v_scale) is compacted in "
+                            "place only: a dense out= pair has no channel for the kept rows' "
+                            "scales")
         if d != "inplace":
             E._check_dest_tensors(i, k, v, d[0], d[1])
             continue
@@ -412,15 +512,16 @@ def _compress_ragged(fn, layers, dests, kwargs):
          for pk in layers], kwargs, True)
     # launch groups: engine jobs by their (order, algo); copy-only moves ride in a group of their
     # geometry (any order / algo: nothing is selected)
-    geos = [(pk.k_pool.get_device(), pk.k_pool.dtype, pk.k_pool.size(1), pk.k_pool.size(3))
-            for pk in layers]
+    # (scaled layers launch apart: kvc_launch_scaled takes a scale description per layer)
+    geos = [(pk.k_pool.get_device(), pk.k_pool.dtype, pk.k_pool.size(1), pk.k_pool.size(3),
+             pk.scaled) for pk in layers]
     groups = {}
     for li, bs, how in spans:
         if how is not None:
             groups.setdefault(geos[li] + how, {}).setdefault(li, []).extend(bs)
     for li, bs, how in spans:
         if how is None:
-            key = next((k for k in groups if k[:4] == geos[li]),
+            key = next((k for k in groups if k[:5] == geos[li]),
                        geos[li] + (N.KVC_ASC, N.KVC_ALGO_SORT))
             groups.setdefault(key, {}).setdefault(li, []).extend(bs)
     if not groups:
@@ -442,13 +543,14 @@ def _compress_ragged(fn, layers, dests, kwargs):
         dev[device] = torch.from_numpy(host[device].view(np.uint8)).to(
             torch.device("cuda", device))
     launches = []
-    for (device, dtype, H, D, order, algo), lis, slot in plans:  # plan (and check) every group
+    for (device, dtype, H, D, sc, order, algo), lis, slot in plans:  # plan (and check) every group
         with torch.cuda.device(device):
             p = E._params(dtype, B, H, D, order, algo, False)
             n = len(lis)
             table = np.zeros(n, dtype=N.LAYER_DTYPE)
             pages = np.zeros(n, dtype=N.PAGES_DTYPE)
             ragged = np.zeros(n, dtype=N.RAGGED_DTYPE)
+            scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
             off = int(start[device][slot])
             for i, li in enumerate(lis):
                 pk = layers[li]
@@ -462,22 +564,26 @@ def _compress_ragged(fn, layers, dests, kwargs):
                             kp.size(0), 1, 0)
                 step = off + i * B * N.SEQ_DTYPE.itemsize
                 ragged[i] = (host[device].ctypes.data + step, dev[device].data_ptr() + step)
-            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged)
-            launches.append((device, p, table, ws, info, pages, ragged))
-    for device, p, table, ws, info, pages, ragged in launches:
+                if sc:
+                    scales[i] = pk.scales_row()
+            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged, scales)
+            launches.append((device, p, table, ws, info, pages, ragged, scales))
+    for device, p, table, ws, info, pages, ragged, scales in launches:
         with torch.cuda.device(device):
             E._launch(p, table, ws, info, torch.cuda.current_stream(device), p.phases, None, pages,
-                      ragged)
+                      ragged, scales)
     return new_len
 
 
 def run_jobs(jobs, order, algo):
-    """Launch checked paged jobs: one kvc_launch_paged per (device, dtype, B, H, D) group."""
+    """Launch checked paged jobs: one kvc_launch_paged per (device, dtype, B, H, D) group --
+    kvc_launch_scaled for the group's layers that carry scales."""
     groups = {}
     for j in jobs:
         B, H, _, D = j.paged.shape
-        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D), []).append(j)
-    for (device, dtype, B, H, D), js in groups.items():
+        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D, j.paged.scaled),
+                          []).append(j)
+    for (device, dtype, B, H, D, sc), js in groups.items():
         external = any(j.ext_index is not None for j in js)
         if external and not all(j.ext_index is not None or j.n_select == 0 for j in js):
             raise RuntimeError("mixed external / engine-selected layers in one group")
@@ -488,6 +594,7 @@ def run_jobs(jobs, order, algo):
             table = np.zeros(n, dtype=N.LAYER_DTYPE)
             pages = np.zeros(n, dtype=N.PAGES_DTYPE)
             dests = np.zeros(n, dtype=N.DEST_DTYPE)
+            scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
             dense = False
             for i, j in enumerate(js):
                 pk = j.paged
@@ -503,6 +610,10 @@ def run_jobs(jobs, order, algo):
                 t["pool_kernel"], t["score_mode"] = j.pool_kernel, j.score_mode
                 pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
                             kp.size(0), 1 if inplace else 0, 0)
+                if sc:
+                    if not inplace:  # (compress_paged refuses it before anything is planned)
+                        raise TypeError("a scaled layer is compacted in place only")
+                    scales[i] = pk.scales_row()
                 if inplace:
                     t["k_out"], t["v_out"] = t["k"], t["v"]
                 else:
@@ -510,8 +621,8 @@ def run_jobs(jobs, order, algo):
                     t["k_out"], t["v_out"] = j.k_dest.data_ptr(), j.v_dest.data_ptr()
                     dests[i] = (j.k_dest.stride()[:3], j.v_dest.stride()[:3], 0, 0)
             dd = dests if dense else None
-            ws, info = E._upload(p, table, device, js, B, H, dd, pages)
-            E._launch(p, table, ws, info, stream, p.phases, dd, pages)
+            ws, info = E._upload(p, table, device, js, B, H, dd, pages, None, scales)
+            E._launch(p, table, ws, info, stream, p.phases, dd, pages, None, scales)
 
 
 __all__ = ["PagedKV", "compress_paged"]

@@ -78,17 +78,20 @@ enum kvc_dtype {
   KVC_BF16 = 1,
   KVC_F16 = 2,
   /* fp8 K/V caches, the OCP formats (torch.float8_e4m3fn / float8_e5m2; gfx950's native fp8), with
-   * dequantisation scale 1.  Elements are 1 byte: strides, alignment, spans and GATHER units follow
-   * the D-byte rows.  Every fp8 pattern upcasts to bf16 exactly, and the SCORE dtype of an fp8 call
-   * is bf16: the kept positions, the norm region (norm_row_stride counts 2-byte elements), the
-   * tile statistics, the index region and the workspace layout are those of a bf16 call on
-   * K.to(bf16) -- torch.norm's 8-lane FMA order over the D upcast elements, norms rounded to bf16,
-   * u16 keys, NaN patterns as the one NaN key, e5m2 +-inf giving an inf norm.  GATHER copies the
-   * kept rows' BYTES of K and V verbatim: no NaN rewrite, V is never interpreted.  head_dim is 64,
-   * 128 or 256 (else KVC_E_HEADDIM).  The fnuz formats and raw byte tensors have no code; a
-   * general k_scale is out of scope (scaling then rounding can change ties, and kvc_layer_t has no
-   * room for it in ABI 4).  The kvc_attn_* / kvc_heavy_hitters entries refuse them (KVC_E_DTYPE):
-   * attention tensors are not fp8.  Additive within ABI 4: an older library answers KVC_E_DTYPE. */
+   * dequantisation scale 1 (per-token or uniform scales of paged caches compacted in place:
+   * kvc_scales_t, "Per-token-scaled fp8 paged caches" below).  Elements are 1 byte: strides,
+   * alignment, spans and GATHER units follow the D-byte rows.  Every fp8 pattern upcasts to bf16
+   * exactly, and the SCORE dtype of an fp8 call is bf16: the kept positions, the norm region
+   * (norm_row_stride counts 2-byte elements), the tile statistics, the index region and the
+   * workspace layout are those of a bf16 call on K.to(bf16) -- torch.norm's 8-lane FMA order over
+   * the D upcast elements, norms rounded to bf16, u16 keys, NaN patterns as the one NaN key, e5m2
+   * +-inf giving an inf norm.  GATHER copies the kept rows' BYTES of K and V verbatim: no NaN
+   * rewrite, V is never interpreted.  head_dim is 64, 128 or 256 (else KVC_E_HEADDIM).  The fnuz
+   * formats and raw byte tensors have no code; scales of dense K/V calls and of paged calls with
+   * dense outputs are out of scope (kvc_layer_t has no room for them in ABI 4, and a dense output
+   * no channel for the moved scales).  The kvc_attn_* / kvc_heavy_hitters entries refuse them
+   * (KVC_E_DTYPE): attention tensors are not fp8.  Additive within ABI 4: an older library answers
+   * KVC_E_DTYPE. */
   KVC_F8E4M3 = 16,
   KVC_F8E5M2 = 17
 };
@@ -442,6 +445,84 @@ int kvc_plan_ragged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_p
 int kvc_launch_ragged(const kvc_params_t* params, const kvc_layer_t* layers,
                       const kvc_pages_t* pages, const kvc_ragged_t* ragged, int num_layers,
                       void* workspace, size_t workspace_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-token-scaled fp8 paged caches (additive within ABI 4: no existing struct, size or entry
+ * changes; a library without these two entries does not export them).
+ *
+ * A per-token quantised fp8 cache keeps one fp32 dequantisation scale per (page, head, slot) in a
+ * scale pool beside the K pool and one beside the V pool, addressed through the SAME block table:
+ * the scale of logical row s of (b, h) is the float at
+ *     scale + (block_table[b * table_stride + (s >> log2 P)] * page_stride + h * stride[0]
+ *              + (s & (P - 1)) * stride[1]) * 4
+ * (element strides of 4-byte floats; a pool stored [N, H, P] or [N, P, H] alike).  With a
+ * kvc_scales_t per layer:
+ *
+ *   SCORE stores, for a key row with scale s,
+ *       bf16( torch.norm(K8.to(float32), dim=-1) * |s| )
+ *     -- the fp32 norm the unscaled fp8 call rounds (torch.norm's 8-lane FMA order over the D
+ *     upcast elements, correctly rounded sqrt), ONE fp32 multiply by |s| (round to nearest even,
+ *     denormal products kept), and one bf16 rounding in place of the unscaled call's.  NaN or inf
+ *     in s or in the row give what those operations give (0 * inf is NaN); a negative scale
+ *     counts by its magnitude.  The tile statistics, SELECT and everything behind them see these
+ *     stored norms and are the bf16 call on them.  V scales are never read for scoring.
+ *   GATHER moves, with output row t, the 4 BYTES of the K scale and of the V scale of its source
+ *     row src(t) into the slots of logical row t, in the same pass of the same workgroup that
+ *     moves the row (a row's scale is part of the row: the in-place ordering argument is
+ *     unchanged).  No float is interpreted: a NaN scale keeps its payload.  Sink rows are not
+ *     touched; rows [n_out, seq_len), spare pages and every other scale-pool byte keep their
+ *     contents.  A row whose destination page id is out of range drops its scale stores with its
+ *     row stores (KVC_DEV_INDEX_RANGE).
+ *
+ * A UNIFORM scale (KVC_SCALE_K_UNIFORM / _V_UNIFORM: vLLM's per-tensor k_scale) is ONE device
+ * float that serves every token: the K one is read by SCORE, on the device, with the formula
+ * above and never written; the V one is ignored.  It changes the result only through rounding
+ * ties (every row of a sequence is scaled alike).  KVC_SCALE_K_NONE / _V_NONE: no scale on that
+ * side (scale 1; the pointer is not read).
+ *
+ * Rules: every layer of the call is paged and in_place == 1 (KVC_E_ARG otherwise -- a dense
+ * output has no channel for the moved scales); dtype is an fp8 format (KVC_E_DTYPE); flags has no
+ * unknown bit, at most one of UNIFORM / NONE per side, reserved is 0 (KVC_E_ARG); a pointer that
+ * is read is non-NULL (KVC_E_ARG) and 4-byte aligned (KVC_E_ALIGN); a per-token pool has a
+ * non-zero stride on every dim larger than 1 -- pages when num_pages > 1, heads, slots
+ * (KVC_E_ARG: a scale shared by the heads would be written by `heads` workgroups that keep
+ * different rows).  The caller promises that the scale pools alias neither each other nor the
+ * K / V pools, and that what the paged contract says of written pages holds for their scales.
+ * Plan info and workspace layout are those of the unscaled call.  Phases may be launched
+ * separately: SCORE alone writes the scaled norms, GATHER alone moves the scales.
+ * external_index / KVC_FLAG_SHARED_INDEX work as for kvc_launch_paged when ragged == NULL.
+ * ------------------------------------------------------------------------------------------- */
+enum kvc_scale_flag {
+  KVC_SCALE_K_UNIFORM = 1, /* k_scale points at one float                     */
+  KVC_SCALE_V_UNIFORM = 2, /* v_scale points at one float (never read)        */
+  KVC_SCALE_K_NONE = 4,    /* no K scale: keys scored as with scale 1          */
+  KVC_SCALE_V_NONE = 8     /* no V scale: nothing moves beside the V rows      */
+};
+
+typedef struct kvc_scales {
+  float* k_scale;         /* device: K scale pool base (page 0), or the one uniform float  */
+  float* v_scale;
+  int64_t k_page_stride;  /* floats between consecutive pages of the K scale pool          */
+  int64_t v_page_stride;
+  int64_t k_stride[2];    /* float strides of the heads and of the slots inside a page     */
+  int64_t v_stride[2];
+  int32_t flags;          /* OR of enum kvc_scale_flag                                     */
+  int32_t reserved;       /* 0                                                             */
+} kvc_scales_t;           /* 72 bytes */
+
+/* kvc_plan_ragged for scaled layers: scales[i] belongs to layers[i] / pages[i].  scales == NULL
+ * behaves exactly like kvc_plan_ragged; ragged == NULL plans the single-length paged call
+ * (kvc_plan_paged without dests).  Pure host function. */
+int kvc_plan_scaled(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, const kvc_scales_t* scales, int num_layers,
+                    kvc_plan_info_t* info);
+
+/* kvc_launch_ragged for scaled layers (scales == NULL: exactly kvc_launch_ragged).  Re-validates
+ * as kvc_plan_scaled does; the kernels receive the scale descriptions by value. */
+int kvc_launch_scaled(const kvc_params_t* params, const kvc_layer_t* layers,
+                      const kvc_pages_t* pages, const kvc_ragged_t* ragged,
+                      const kvc_scales_t* scales, int num_layers, void* workspace,
+                      size_t workspace_bytes, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |
