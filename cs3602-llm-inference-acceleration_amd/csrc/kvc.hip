@@ -41,6 +41,7 @@
 #include "kvc_gather_dest.h"    // gather_dest_kernel (kvc_launch_dest)
 #include "kvc_paged.h"          // score_paged_kernel, gather_paged_kernel (kvc_launch_paged)
 #include "kvc_ragged.h"         // the per-sequence-record kernels (kvc_launch_ragged)
+#include "kvc_repage.h"         // GATHER through a destination block table (kvc_launch_repage)
 
 namespace kvc {
 
@@ -342,9 +343,11 @@ static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc
 // under a layer's rules, the layers' segment fields set to (fill) or compared with (launch) the
 // envelope of their records, then plan_impl and the page checks on that envelope.
 // ragged == nullptr: plan_paged_impl without destinations.
+// repage (plan_repage_impl): the layers are written through a destination table, out of place --
+// in_place must be 0 and the records are free of the in-place row-map rule.
 static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
                             const kvc_ragged_t* ragged, int nl, kvc_plan_info_t* info,
-                            bool fill) {
+                            bool fill, bool repage = false) {
   if (!ragged) return plan_paged_impl(p, layers, pages, nullptr, nl, info, fill);
   if (!p || nl < 0 || (nl > 0 && (!layers || !pages)) || p->batch < 1) return KVC_E_ARG;
   if (p->external_index || (p->flags & (KVC_FLAG_SHARED_INDEX | KVC_FLAG_GATHER_FIXED |
@@ -354,7 +357,7 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
     const kvc_ragged_t& r = ragged[l];
     if (!r.host || !r.dev || ((uintptr_t)r.host & 3u) || ((uintptr_t)r.dev & 15u))
       return KVC_E_ARG;
-    if (pages[l].in_place != 1) return KVC_E_ARG;
+    if (pages[l].in_place != (repage ? 0 : 1)) return KVC_E_ARG;
     kvc_layer_t e = layers[l];  // the envelope
     e.seq_len = e.zone_start = e.zone_len = e.n_select = e.sink_len = e.tail_start = 0;
     e.tail_len = e.pool_kernel = 0;
@@ -374,7 +377,7 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
       kvc_layer_t y = e;  // the record as a layer: the row-map rule's argument
       y.zone_start = q.zone_start, y.zone_len = q.zone_len, y.n_select = q.n_select;
       y.sink_len = q.sink_len, y.tail_start = q.tail_start, y.tail_len = q.tail_len;
-      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
+      if (!repage && !in_place_row_map_ok(y)) return KVC_E_ARG;
       const bool sel = layer_selects(y);
       selects |= sel;
       e.seq_len = S > e.seq_len ? S : e.seq_len;
@@ -416,8 +419,8 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
 // of every layer.  scales == nullptr: plan_ragged_impl alone.
 static int plan_scaled_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
                             const kvc_ragged_t* ragged, const kvc_scales_t* scales, int nl,
-                            kvc_plan_info_t* info, bool fill) {
-  int rc = plan_ragged_impl(p, layers, pages, ragged, nl, info, fill);
+                            kvc_plan_info_t* info, bool fill, bool repage = false) {
+  int rc = plan_ragged_impl(p, layers, pages, ragged, nl, info, fill, repage);
   if (rc != KVC_OK || !scales) return rc;
   if (nl > 0 && !pages) return KVC_E_ARG;  // every scaled layer is paged
   if (!is_fp8(p->dtype)) return KVC_E_DTYPE;
@@ -426,8 +429,9 @@ static int plan_scaled_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
   for (int l = 0; l < nl; ++l) {
     const kvc_scales_t& z = scales[l];
     const kvc_pages_t& g = pages[l];
-    // a dense output has no channel for the moved scales
-    if (g.in_place != 1 || layers[l].k_out != layers[l].k || layers[l].v_out != layers[l].v)
+    // a dense output has no channel for the moved scales (a paged destination has: dscales)
+    if (!repage &&
+        (g.in_place != 1 || layers[l].k_out != layers[l].k || layers[l].v_out != layers[l].v))
       return KVC_E_ARG;
     if ((z.flags & ~kKnown) || z.reserved != 0 ||
         ((z.flags & KVC_SCALE_K_UNIFORM) && (z.flags & KVC_SCALE_K_NONE)) ||
@@ -457,6 +461,74 @@ static int plan_scaled_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
   }
   return KVC_OK;
 }
+
+// kvc_plan_repage / kvc_launch_repage (include/kvc.h, "Paged destinations"): plan_scaled_impl
+// without the in-place rules, then the destination description -- and, for scaled layers, the
+// destination scale pools -- of every layer with output.  pdests == nullptr: plan_scaled_impl.
+static int plan_repage_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
+                            const kvc_ragged_t* ragged, const kvc_scales_t* scales,
+                            const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int nl,
+                            kvc_plan_info_t* info, bool fill) {
+  if (!pdests) return plan_scaled_impl(p, layers, pages, ragged, scales, nl, info, fill);
+  if (nl > 0 && !pages) return KVC_E_ARG;  // every layer with a paged destination is paged
+  int rc = plan_scaled_impl(p, layers, pages, ragged, scales, nl, info, fill, true);
+  if (rc != KVC_OK) return rc;
+  if (scales && !dscales) return KVC_E_ARG;
+  const int es = esize(p->dtype);
+  const int64_t H = p->heads;
+  constexpr int kKnown =
+      KVC_SCALE_K_UNIFORM | KVC_SCALE_V_UNIFORM | KVC_SCALE_K_NONE | KVC_SCALE_V_NONE;
+  for (int l = 0; l < nl; ++l) {
+    const kvc_layer_t& y = layers[l];  // (ragged: the envelope, n_out the largest record's)
+    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
+    if (n_out == 0) continue;
+    if (pages[l].in_place != 0) return KVC_E_ARG;
+    const kvc_page_dest_t& d = pdests[l];
+    if (!d.block_table || ((uintptr_t)d.block_table & 3u) || d.num_pages < 1 || d.page_size < 1 ||
+        d.page_size > 65536 || (d.page_size & (d.page_size - 1)))
+      return KVC_E_ARG;
+    const int64_t P = d.page_size;
+    if (d.table_stride < (n_out + P - 1) / P) return KVC_E_ARG;
+    const bool heads = H > 1, slots = P > 1 && n_out > 1, pgs = d.num_pages > 1;
+    // a zero stride would make different output rows one address
+    if ((heads && (d.k_stride[0] == 0 || d.v_stride[0] == 0)) ||
+        (slots && (d.k_stride[1] == 0 || d.v_stride[1] == 0)) ||
+        (pgs && (d.k_page_stride == 0 || d.v_page_stride == 0)))
+      return KVC_E_ARG;
+    // (plan_impl has checked k_out / v_out themselves)
+    if ((heads && ((d.k_stride[0] * es) % 16 || (d.v_stride[0] * es) % 16)) ||
+        (slots && ((d.k_stride[1] * es) % 16 || (d.v_stride[1] * es) % 16)) ||
+        (pgs && ((d.k_page_stride * es) % 16 || (d.v_page_stride * es) % 16)))
+      return KVC_E_ALIGN;
+    if (!scales) continue;
+    const kvc_scales_t& z = scales[l];
+    const kvc_scales_t& dz = dscales[l];
+    if ((dz.flags & ~kKnown) || dz.reserved != 0 || dz.flags != z.flags) return KVC_E_ARG;
+    const struct {
+      const float* ptr;
+      int64_t page, head, slot;
+      bool pool;
+    } side[2] = {{dz.k_scale, dz.k_page_stride, dz.k_stride[0], dz.k_stride[1],
+                  !(z.flags & (KVC_SCALE_K_NONE | KVC_SCALE_K_UNIFORM))},
+                 {dz.v_scale, dz.v_page_stride, dz.v_stride[0], dz.v_stride[1],
+                  !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM))}};
+    for (const auto& s : side) {
+      if (!s.pool) continue;  // uniform or absent: nothing moves, the pointer is not read
+      if (!s.ptr) return KVC_E_ARG;
+      if ((uintptr_t)s.ptr & 3u) return KVC_E_ALIGN;
+      if ((pgs && s.page == 0) || (heads && s.head == 0) || (P > 1 && s.slot == 0))
+        return KVC_E_ARG;
+    }
+  }
+  return KVC_OK;
+}
+
+// The destination side of a repage launch (kvc_launch_repage), handed to launch_chunk /
+// launch_chunk_ragged: their GATHER then is launch_gather_repage's.
+struct RepageArgs {
+  const kvc_page_dest_t* pdests;
+  const kvc_scales_t* dscales;  // with scales only
+};
 
 // Every launch goes through hipLaunchKernel, whose return value is this launch's own status (a
 // caller's pending HIP error is neither consumed nor reported as ours).
@@ -604,6 +676,59 @@ static int launch_gather_paged(const PagesChunk& C, int nl, int H, int BH, const
                   istride, shared, status);
 }
 
+// GATHER of a repage chunk (kvc_repage.h): grid (rows, passes of the chunk's longest output --
+// a ragged layer's envelope), the chunk's tables by value; the scale-carrying instances (fp8 rows,
+// cn <= kRepageScLayers) when scales move.  `ragged`: the chunk's entries, or nullptr.
+template <typename C>
+static void fill_repage_tables(C* c, const kvc_layer_t* layers, const kvc_pages_t* pages,
+                               const kvc_page_dest_t* pdests, int cn) {
+  memset(c, 0, sizeof(*c));
+  memcpy(c->l, layers, (size_t)cn * sizeof(kvc_layer_t));
+  memcpy(c->p, pages, (size_t)cn * sizeof(kvc_pages_t));
+  memcpy(c->d, pdests, (size_t)cn * sizeof(kvc_page_dest_t));
+}
+template <int DT, int NC>
+static int launch_gather_repage(const kvc_layer_t* layers, const kvc_pages_t* pages,
+                                const kvc_ragged_t* ragged, const kvc_scales_t* scales,
+                                const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int cn,
+                                int H, int BH, const int32_t* idx, int64_t istride, int shared,
+                                uint32_t* status, hipStream_t s) {
+  const dim3 grid = pass_grid<NC>(layers, cn, BH, [](int) { return 0; });
+  if (scales) {
+    if constexpr (is_fp8(DT)) {
+      if (cn > kRepageScLayers) return KVC_E_ARG;
+      if (ragged) {
+        RepageRaggedScChunk C;
+        fill_repage_tables(&C, layers, pages, pdests, cn);
+        memcpy(C.z, scales, (size_t)cn * sizeof(kvc_scales_t));
+        memcpy(C.dz, dscales, (size_t)cn * sizeof(kvc_scales_t));
+        for (int l = 0; l < cn; ++l) C.s[l] = ragged[l].dev;
+        return launch_k(gather_repage_ragged_sc_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s,
+                        C, H, BH, idx, istride, status);
+      }
+      RepageScChunk C;
+      fill_repage_tables(&C, layers, pages, pdests, cn);
+      memcpy(C.z, scales, (size_t)cn * sizeof(kvc_scales_t));
+      memcpy(C.dz, dscales, (size_t)cn * sizeof(kvc_scales_t));
+      return launch_k(gather_repage_sc_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, C, H, BH,
+                      idx, istride, shared, status);
+    } else {
+      return KVC_E_DTYPE;  // (plan_scaled_impl: scales belong to fp8 rows)
+    }
+  }
+  if (ragged) {
+    RepageRaggedChunk C;
+    fill_repage_tables(&C, layers, pages, pdests, cn);
+    for (int l = 0; l < cn; ++l) C.s[l] = ragged[l].dev;
+    return launch_k(gather_repage_ragged_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, C, H,
+                    BH, idx, istride, status);
+  }
+  RepageChunk C;
+  fill_repage_tables(&C, layers, pages, pdests, cn);
+  return launch_k(gather_repage_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, C, H, BH, idx,
+                  istride, shared, status);
+}
+
 // The 512-thread selection kernels (zones up to kSmallZone) over n_cap positions: the candidate
 // capacity that fits the LDS budget (*cap) and the dynamic LDS bytes; wave segment kWaveSegSmall
 static size_t small_sel_lds(int n_cap, int key_size, int* cap) {
@@ -662,12 +787,14 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
 // layers' block tables (kvc_paged.h), SELECT as with dests.
 // scales != nullptr (kvc_launch_scaled; fp8, paged, in place): SCORE and GATHER are the scaled
 // instances, which also read / move the layers' scale words.
+// rp != nullptr (kvc_launch_repage; paged, out of place): SCORE and SELECT as above, GATHER through
+// the layers' destination tables (launch_gather_repage).
 template <int DT, int NC>
 static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, const kvc_layer_t* layers,
                         int nl, int c0, int cn, char* w, hipStream_t s,
                         const kvc_dest_t* dests = nullptr,
                         const kvc_pages_t* pages = nullptr,
-                        const kvc_scales_t* scales = nullptr) {
+                        const kvc_scales_t* scales = nullptr, const RepageArgs* rp = nullptr) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
   constexpr int SDT = score_dt(DT);  // the selection's runtime dtype (bf16 for fp8 rows)
@@ -777,6 +904,14 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                            long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if (rp) {
+    if (!((p->phases & KVC_PHASE_GATHER) && max_part > 0)) return rc;
+    return launch_gather_repage<DT, NC>(layers + c0, pages + c0, nullptr,
+                                        scales ? scales + c0 : nullptr, rp->pdests + c0,
+                                        scales ? rp->dscales + c0 : nullptr, cn, H, BH, idx,
+                                        istride, (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0,
+                                        status, s);
+  }
   if constexpr (is_fp8(DT)) {
     if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && scales)  // every layer in place
       return launch_k(gather_paged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
@@ -843,7 +978,8 @@ template <int DT, int NC>
 static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& info,
                                const kvc_layer_t* layers, const kvc_pages_t* pages,
                                const kvc_ragged_t* ragged, int nl, int c0, int cn, char* w,
-                               hipStream_t s, const kvc_scales_t* scales = nullptr) {
+                               hipStream_t s, const kvc_scales_t* scales = nullptr,
+                               const RepageArgs* rp = nullptr) {
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
   const int H = p->heads, BH = p->batch * p->heads;
   char* norms = w + info.norm_offset;
@@ -897,6 +1033,13 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
                                   istride, long_zone, scratch, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
+  if (rp) {  // kvc_launch_repage: out of place, through the destination tables
+    if (!((p->phases & KVC_PHASE_GATHER) && max_out > 0)) return rc;
+    return launch_gather_repage<DT, NC>(layers + c0, pages + c0, ragged + c0,
+                                        scales ? scales + c0 : nullptr, rp->pdests + c0,
+                                        scales ? rp->dscales + c0 : nullptr, cn, H, BH, idx,
+                                        istride, 0, status, s);
+  }
   if constexpr (is_fp8(DT)) {
     if ((p->phases & KVC_PHASE_GATHER) && max_out > 0 && scales)
       return launch_k(gather_ragged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
@@ -1226,6 +1369,48 @@ int kvc_launch_scaled(const kvc_params_t* p, const kvc_layer_t* layers, const kv
           return launch_chunk_ragged<DT, NC>(p, info, layers, pages, ragged, nl, c0, cn, w, s,
                                              scales);
         return launch_chunk<DT, NC>(p, info, layers, nl, c0, cn, w, s, nullptr, pages, scales);
+      });
+    });
+  }
+  return rc;
+}
+
+int kvc_plan_repage(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, const kvc_scales_t* scales,
+                    const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int num_layers,
+                    kvc_plan_info_t* info) {
+  return kvc::plan_repage_impl(params, layers, pages, ragged, scales, pdests, dscales, num_layers,
+                               info, true);
+}
+
+int kvc_launch_repage(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
+                      const kvc_ragged_t* ragged, const kvc_scales_t* scales,
+                      const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int nl, void* ws,
+                      size_t ws_bytes, kvc_stream_t stream) {
+  using namespace kvc;
+  if (!pdests) return kvc_launch_scaled(p, layers, pages, ragged, scales, nl, ws, ws_bytes, stream);
+  kvc_plan_info_t info;
+  int rc = plan_repage_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, scales, pdests,
+                            dscales, nl, &info, false);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0) return KVC_OK;
+  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  const int nc = p->head_dim * esize(p->dtype) / 16;
+  const RepageArgs rp = {pdests, dscales};
+  // layers per argument chunk: the scale-carrying copy takes two scale descriptions per layer
+  const int step = scales ? kRepageScLayers : kPagedLayers;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
+    const int cn = nl - c0 < step ? nl - c0 : step;
+    rc = with_kv_dtype(p->dtype, [&](auto dt) {
+      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
+        constexpr int DT = decltype(dt)::value, NC = decltype(ncv)::value;
+        if (ragged)
+          return launch_chunk_ragged<DT, NC>(p, info, layers, pages, ragged, nl, c0, cn, w, s,
+                                             scales, &rp);
+        return launch_chunk<DT, NC>(p, info, layers, nl, c0, cn, w, s, nullptr, pages, scales,
+                                    &rp);
       });
     });
   }

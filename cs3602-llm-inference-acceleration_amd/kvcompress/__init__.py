@@ -10,7 +10,7 @@ from .benchmark import (benchmark, measure_generation_metrics, print_benchmark_s
 from .evaluate import compare_methods, evaluate_baseline, evaluate_with_compression
 from .methods import (COMPRESS_METHODS, fix_size_l2_compress, get_compress_fn, l2_compress,
                       list_methods, register_method, streaming_llm_compress)
-from .paged import PagedKV, compress_paged  # extension: paged caches
+from .paged import PagedDest, PagedKV, compress_paged  # extension: paged caches
 from .utils import (get_cache_info, get_cache_size_mb, get_seq_len, normalize_kv_cache,
                     to_dynamic_cache)
 

@@ -45,6 +45,9 @@ class Segments:
     # compress_paged: the layer's PagedKV.  keys / values are then stand-ins of the layer's shape
     # (nothing is read from them) and the job is launched by paged.run_jobs (kvc_launch_paged)
     paged: Optional[object] = None
+    # compress_paged: the layer's PagedDest, already bound to its PagedKV (k_dest / v_dest are
+    # then stand-ins too; the job is launched with kvc_launch_repage)
+    page_dest: Optional[object] = None
 
 
 # fp8 K/V: the OCP formats only (gfx950's native fp8, dequantisation scale 1).  Keys are scored
@@ -306,10 +309,14 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None, scales=None):
+def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None, scales=None,
+            pdests=None, dscales=None):
     """Plan one table and allocate its workspace.  The table itself travels in the kernels'
     arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    if scales is not None:  # scaled fp8 paged layers, compacted in place (ragged or not)
+    if pdests is not None:  # paged layers delivered through a second block table
+        rc, info = N.plan_repage(params, table, pages, ragged, scales, pdests, dscales)
+        N.check(rc, "kvc_plan_repage")
+    elif scales is not None:  # scaled fp8 paged layers, compacted in place (ragged or not)
         rc, info = N.plan_scaled(params, table, pages, ragged, scales)
         N.check(rc, "kvc_plan_scaled")
     elif ragged is not None:
@@ -337,7 +344,7 @@ def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None
 
 
 def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, ragged=None,
-            scales=None):
+            scales=None, pdests=None, dscales=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
@@ -348,7 +355,10 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, rag
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        if scales is not None:
+        if pdests is not None:
+            rc = N.launch_repage(params, table, pages, ragged, scales, pdests, dscales,
+                                 ws.data_ptr(), int(info.workspace_bytes), stream.cuda_stream)
+        elif scales is not None:
             rc = N.launch_scaled(params, table, pages, ragged, scales, ws.data_ptr(),
                                  int(info.workspace_bytes), stream.cuda_stream)
         elif ragged is not None:
@@ -365,7 +375,8 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, rag
                                stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch_scaled" if scales is not None else
+        N.check(rc, "kvc_launch_repage" if pdests is not None else
+                "kvc_launch_scaled" if scales is not None else
                 "kvc_launch_ragged" if ragged is not None else
                 "kvc_launch_paged" if pages is not None else
                 "kvc_launch" if dests is None else "kvc_launch_dest")
@@ -909,7 +920,10 @@ def _span(t, n):
 
 
 def _check_dest(j: Segments):
-    """The destination of one job: _check_dest_tensors, then what depends on its segments."""
+    """The destination of one job: _check_dest_tensors, then what depends on its segments.
+    (compress_paged does not call this for a job with a PagedDest: its k_dest / v_dest are
+    stride-0 stand-ins that say nothing about memory, so the span checks below would compare
+    meaningless addresses; paged.py checks the table's capacity and the pools' spans itself.)"""
     if j.dest_verified:
         return
     li, k, v = j.layer_idx, j.keys, j.values

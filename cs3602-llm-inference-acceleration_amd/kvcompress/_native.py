@@ -77,6 +77,14 @@ SCALES_DTYPE = np.dtype([
 assert SCALES_DTYPE.itemsize == 72
 SCALE_K_UNIFORM, SCALE_V_UNIFORM, SCALE_K_NONE, SCALE_V_NONE = 1, 2, 4, 8  # enum kvc_scale_flag
 
+# struct kvc_page_dest (include/kvc.h: paged destinations) -- 72 bytes
+PAGE_DEST_DTYPE = np.dtype([
+    ("block_table", "<u8"), ("table_stride", "<i8"), ("k_page_stride", "<i8"),
+    ("v_page_stride", "<i8"), ("k_stride", "<i8", (2,)), ("v_stride", "<i8", (2,)),
+    ("page_size", "<i4"), ("num_pages", "<i4"),
+])
+assert PAGE_DEST_DTYPE.itemsize == 72
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -117,7 +125,7 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
            "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
            "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged",
-           "kvc_plan_scaled", "kvc_launch_scaled")
+           "kvc_plan_scaled", "kvc_launch_scaled", "kvc_plan_repage", "kvc_launch_repage")
 
 _lib = None
 
@@ -177,6 +185,13 @@ def lib():
                                       ctypes.POINTER(PlanInfo)]
         L.kvc_launch_scaled.restype = i32
         L.kvc_launch_scaled.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, i32, vp,
+                                        ctypes.c_size_t, vp]
+    if hasattr(L, "kvc_plan_repage"):  # additive within ABI 4, like the scaled entries
+        L.kvc_plan_repage.restype = i32
+        L.kvc_plan_repage.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, vp, vp, i32,
+                                      ctypes.POINTER(PlanInfo)]
+        L.kvc_launch_repage.restype = i32
+        L.kvc_launch_repage.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, vp, vp, i32, vp,
                                         ctypes.c_size_t, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
@@ -334,6 +349,37 @@ def launch_scaled(params, table, pages, ragged, scales, ws_ptr, ws_bytes, stream
                                    _opt(ragged, RAGGED_DTYPE, len(table)),
                                    _opt(scales, SCALES_DTYPE, len(table)), len(table), ws_ptr,
                                    ws_bytes, stream_ptr)
+
+
+def _need_repage_entries():
+    if not hasattr(lib(), "kvc_plan_repage"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_plan_repage / kvc_launch_repage (built "
+                                 "before paged destinations); they need the current library")
+
+
+def plan_repage(params, table, pages, ragged, scales, pdests, dscales):
+    """kvc_plan_repage: `pdests` is a PAGE_DEST_DTYPE array, one entry per layer, or None (=
+    kvc_plan_scaled); `dscales` a SCALES_DTYPE array (the destination scale pools) or None."""
+    info = PlanInfo()
+    _need_repage_entries()
+    n = len(table)
+    rc = lib().kvc_plan_repage(ctypes.byref(params), table.ctypes.data,
+                               _opt(pages, PAGES_DTYPE, n), _opt(ragged, RAGGED_DTYPE, n),
+                               _opt(scales, SCALES_DTYPE, n), _opt(pdests, PAGE_DEST_DTYPE, n),
+                               _opt(dscales, SCALES_DTYPE, n), n, ctypes.byref(info))
+    return rc, info
+
+
+def launch_repage(params, table, pages, ragged, scales, pdests, dscales, ws_ptr, ws_bytes,
+                  stream_ptr):
+    """kvc_launch_repage (pdests None = kvc_launch_scaled)."""
+    _need_repage_entries()
+    n = len(table)
+    return lib().kvc_launch_repage(ctypes.byref(params), table.ctypes.data,
+                                   _opt(pages, PAGES_DTYPE, n), _opt(ragged, RAGGED_DTYPE, n),
+                                   _opt(scales, SCALES_DTYPE, n),
+                                   _opt(pdests, PAGE_DEST_DTYPE, n),
+                                   _opt(dscales, SCALES_DTYPE, n), n, ws_ptr, ws_bytes, stream_ptr)
 
 
 def attn_accumulate(params, table, stream_ptr):

@@ -45,7 +45,8 @@ class PagedKV:
     (vLLM's per-tensor k_scale; read on the device, never synchronised on).  Keys are then ranked
     by bf16(norm(K8) * |k_scale|) and the scales of the kept rows move with them (include/kvc.h,
     "Per-token-scaled fp8 paged caches").  A uniform scale changes a result only through rounding
-    ties; a uniform or absent v_scale is ignored.  Scaled layers are compacted in place only.
+    ties; a uniform or absent v_scale is ignored.  Scaled layers are compacted in place or delivered
+    to a PagedDest (no dense out= pair: it has no channel for the scales).
     A scale tensor of exactly one element counts as uniform whatever its shape -- a
     [1, 1, 1] pool of a one-page, one-head, one-slot cache included: it has one row, whose scale
     need not move.  That the scale pools alias neither each other, nor the K / V pools, nor the
@@ -250,6 +251,211 @@ class PagedKV:
         return tuple(pool[pg, :, slot].permute(0, 2, 1, 3) for pool in (self.k_pool, self.v_pool))
 
 
+class PagedDest:
+    """Where one paged layer's compressed sequence goes when it must not be compacted in place
+    (include/kvc.h, "Paged destinations"): an int32 `block_table` [B, >= ceil(n / page_size)] of
+    DESTINATION page ids on the pools' device, and optionally destination pools `k_pool` / `v_pool`
+    -- `[num_pages', H, page_size', D]` views of the source's dtype, H and D under PagedKV's stride
+    and alignment rules; page size and pool size need not equal the source's.  Without pools the
+    rows go into fresh pages of the SOURCE pools (and, for a per-token-scaled layer, the kept rows'
+    scales into the source scale pools' slots of those pages).  With pools of its own a
+    per-token-scaled layer needs `k_scale` / `v_scale`: float32 `[num_pages', H, page_size']`
+    views, given exactly for the sides that are per-token on the source.
+
+    Output row t of sequence b lands in slot t % page_size' of page block_table[b, t // page_size'],
+    sink rows included; the source pool is only read, so its pages may be shared between
+    sequences (a cached prefix, forked sequences).  The caller promises that a destination page is
+    neither a page any sequence of the layer reads, nor a destination page of another (layer,
+    sequence), nor a page of the other side (K / V): the tables are device data and are not read
+    (kvcompress.paged.check_repage_tables checks host copies of them).  A destination pool is
+    either the source's own view or disjoint from both source pools, which IS checked."""
+    __slots__ = ("block_table", "k_pool", "v_pool", "k_scale", "v_scale")
+
+    def __init__(self, block_table, k_pool=None, v_pool=None, k_scale=None, v_scale=None):
+        for name, t in (("block_table", block_table), ("k_pool", k_pool), ("v_pool", v_pool),
+                        ("k_scale", k_scale), ("v_scale", v_scale)):
+            if not isinstance(t, torch.Tensor) and not (t is None and name != "block_table"):
+                raise TypeError(f"PagedDest: {name} must be a tensor, got {type(t).__name__}")
+        if (k_pool is None) != (v_pool is None):
+            raise ValueError("PagedDest: give both k_pool and v_pool, or neither (the source's)")
+        if k_pool is None and (k_scale is not None or v_scale is not None):
+            raise ValueError("PagedDest: k_scale / v_scale belong to destination pools of their "
+                             "own; without k_pool / v_pool the source's scale pools are used")
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or \
+                (block_table.stride(1) != 1 and block_table.size(1) > 1):
+            raise ValueError("PagedDest: block_table must be an int32 [B, pages per sequence] "
+                             "tensor with a contiguous last dim; got "
+                             f"{block_table.dtype} {tuple(block_table.shape)}")
+        if not block_table.is_cuda:
+            raise ValueError("PagedDest: block_table must be on the pools' ROCm device; got "
+                             f"{block_table.device}")
+        self.block_table, self.k_pool, self.v_pool = block_table, k_pool, v_pool
+        self.k_scale, self.v_scale = k_scale, v_scale
+
+    def bind(self, i, pk):
+        """This destination resolved against layer i's PagedKV and checked: a PagedDest whose
+        pools (and scales, for the per-token sides) are tensors.  Raises naming the layer."""
+        what = f"layer {i}: PagedDest"
+        kp, vp = (pk.k_pool, pk.v_pool) if self.k_pool is None else (self.k_pool, self.v_pool)
+        bt = self.block_table
+        if bt.device != pk.k_pool.device or bt.size(0) != pk.block_table.size(0):
+            raise ValueError(f"{what}: block_table {tuple(bt.shape)} on {bt.device}, the layer has "
+                             f"{pk.block_table.size(0)} sequences on {pk.k_pool.device}")
+        _, H, _, D = pk.k_pool.shape
+        for name, t in (("k_pool", kp), ("v_pool", vp)):
+            if t.dtype != pk.k_pool.dtype:
+                raise TypeError(f"{what}: {name} has dtype {t.dtype}, the layer {pk.k_pool.dtype}")
+            if t.dim() != 4 or t.shape != kp.shape or t.size(1) != H or t.size(3) != D:
+                raise ValueError(f"{what}: {name} must be [num_pages, H, page_size, D] with the "
+                                 f"layer's H = {H} and D = {D}, K and V alike; got "
+                                 f"{tuple(t.shape)}")
+        npg, _, P, _ = kp.shape
+        if npg < 1 or P < 1 or P > 65536 or P & (P - 1):
+            raise ValueError(f"{what}: page_size must be a power of two in [1, 65536] and the "
+                             f"pool non-empty; got pools of shape {tuple(kp.shape)}")
+        es = kp.element_size()
+        for name, t in (("k_pool", kp), ("v_pool", vp)):
+            if (t.stride(3) != 1 and D > 1) or any(
+                    (t.stride(d) * es) % 16 and t.size(d) > 1 for d in range(3)):
+                raise ValueError(f"{what}: {name} needs a contiguous last dim and strides that "
+                                 f"are multiples of 16 bytes (a pool is never copied); strides "
+                                 f"{tuple(t.stride())}")
+            if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
+                raise ValueError(f"{what}: {name} has stride 0 on a dim larger than 1")
+            if t.device != pk.k_pool.device:
+                raise ValueError(f"{what}: {name} is on {t.device}, the layer on "
+                                 f"{pk.k_pool.device}")
+            if t.data_ptr() % 16:
+                raise ValueError(f"{what}: {name} pointer not 16-byte aligned (a pool is never "
+                                 "copied)")
+        # a destination pool: the source's own view, or disjoint from both source pools
+        same = []
+        for name, t, src in (("K", kp, pk.k_pool), ("V", vp, pk.v_pool)):
+            own = t is src or (t.data_ptr() == src.data_ptr() and t.shape == src.shape and
+                               t.stride() == src.stride())
+            same.append(own)
+            if own:
+                continue
+            lo, hi = _pool_span(t)
+            for sname, pool in (("K", pk.k_pool), ("V", pk.v_pool)):
+                plo, phi = _pool_span(pool)
+                if lo < phi and plo < hi:
+                    raise ValueError(f"{what}: {name} destination pool overlaps the layer's "
+                                     f"{sname} pool without being the same view")
+        if not all(same):
+            (klo, khi), (vlo, vhi) = _pool_span(kp), _pool_span(vp)
+            if klo < vhi and vlo < khi:
+                raise ValueError(f"{what}: K and V destination pools overlap")
+        # scales: exactly for the sides that are per-token on the source
+        scales = []
+        for side, src, own in (("k_scale", pk.k_scale, self.k_scale),
+                               ("v_scale", pk.v_scale, self.v_scale)):
+            per_token = src is not None and src.numel() != 1
+            t = src if (self.k_pool is None and per_token) else own
+            if per_token and t is None:
+                raise ValueError(f"{what}: the layer's {side} is per-token, so destination pools "
+                                 f"of their own need a destination {side} [num_pages, H, "
+                                 f"page_size] = {(npg, H, P)}")
+            if not per_token and t is not None:
+                raise ValueError(f"{what}: {side} given, but the layer's {side} is not per-token "
+                                 "(nothing of it moves)")
+            if t is not None and t is not src:
+                if t.dtype != torch.float32:
+                    raise TypeError(f"{what}: {side} must be float32, got {t.dtype}")
+                if tuple(t.shape) != (npg, H, P):
+                    raise ValueError(f"{what}: {side} must be [num_pages, H, page_size] = "
+                                     f"{(npg, H, P)}; got {tuple(t.shape)}")
+                if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
+                    raise ValueError(f"{what}: {side} has stride 0 on a dim larger than 1; "
+                                     f"strides {tuple(t.stride())}")
+                if t.device != pk.k_pool.device:
+                    raise ValueError(f"{what}: {side} is on {t.device}, the pools on "
+                                     f"{pk.k_pool.device}")
+                if t.data_ptr() % 4:
+                    raise ValueError(f"{what}: {side} pointer not 4-byte aligned")
+            scales.append(t)
+        return PagedDest(bt, kp, vp, *scales)
+
+    # ---- of a bound destination ----
+    @property
+    def page_size(self):
+        return self.k_pool.size(2)
+
+    @property
+    def capacity(self):
+        """Rows per sequence that the table can address."""
+        return self.block_table.size(1) * self.page_size
+
+    def dest_row(self):
+        """The kvc_page_dest_t (a PAGE_DEST_DTYPE record)."""
+        r = np.zeros(1, dtype=N.PAGE_DEST_DTYPE)[0]
+        kp, vp, bt = self.k_pool, self.v_pool, self.block_table
+        r["block_table"], r["table_stride"] = bt.data_ptr(), bt.stride(0)
+        r["k_page_stride"], r["v_page_stride"] = kp.stride(0), vp.stride(0)
+        r["k_stride"], r["v_stride"] = (kp.stride(1), kp.stride(2)), (vp.stride(1), vp.stride(2))
+        r["page_size"], r["num_pages"] = kp.size(2), kp.size(0)
+        return r
+
+    def scales_row(self, src_row):
+        """The destination kvc_scales_t: the source's flags, the per-token sides' pools."""
+        r = np.zeros(1, dtype=N.SCALES_DTYPE)[0]
+        r["flags"] = src_row["flags"]
+        for side, t in (("k", self.k_scale), ("v", self.v_scale)):
+            if t is not None:
+                r[side + "_scale"] = t.data_ptr()
+                r[side + "_page_stride"] = t.stride(0)
+                r[side + "_stride"] = (t.stride(1), t.stride(2))
+        return r
+
+    def stand_in(self, pk):
+        """(K, V) dense stand-ins [B, H, capacity, D] of the destination, as _stand_in's: the
+        deferred-call machinery carries them as the job's destination; nothing is read from them."""
+        B, H, _, D = pk.shape
+        cap = max(self.capacity, 1)
+        key = (pk.k_pool.dtype, pk.k_pool.device)
+        base = _STAND_INS.get(key)  # one buffer per (dtype, device): no allocation per layer
+        if base is None or base.numel() < cap + D:
+            base = _STAND_INS[key] = torch.empty(max(cap + D, 1 << 16), dtype=key[0],
+                                                 device=key[1])
+        return tuple(base.as_strided((B, H, cap, D), (0, 0, 1, 0), 0) for _ in range(2))
+
+
+# PagedDest.stand_in's storage: the stand-ins of every layer and call are views of one buffer per
+# (dtype, device).  They carry shapes only; nothing is ever read from or written to them.
+_STAND_INS = {}
+
+
+def check_repage_tables(src_table, src_lens, P_src, dst_table, new_lens, P_dst):
+    """A debugging aid for callers of compress_paged(out=[PagedDest...]) whose destination pages
+    are in the SOURCE pool: checks host copies of the tables (numpy integer arrays [B, pages]; the
+    lengths one int per sequence, or one int for all) against the caller's promise.  Raises
+    ValueError naming the first page that is both a source page within `src_lens` and a
+    destination page within `new_lens`, or a destination page used twice; table entries past the
+    lengths are ignored.  Pure host function; compress_paged never calls it."""
+    src_table, dst_table = np.asarray(src_table), np.asarray(dst_table)
+    B = src_table.shape[0]
+    if dst_table.shape[0] != B:
+        raise ValueError(f"check_repage_tables: {B} source rows, {dst_table.shape[0]} destination "
+                         "rows")
+    lens = lambda x: [int(x)] * B if np.ndim(x) == 0 else [int(v) for v in x]  # noqa: E731
+    src_lens, new_lens = lens(src_lens), lens(new_lens)
+    read = {}
+    for b in range(B):
+        for p in src_table[b, :-(-src_lens[b] // P_src)].tolist():
+            read.setdefault(int(p), b)
+    written = {}
+    for b in range(B):
+        for j, p in enumerate(dst_table[b, :-(-new_lens[b] // P_dst)].tolist()):
+            p = int(p)
+            if p in read:
+                raise ValueError(f"check_repage_tables: page {p} is destination page {j} of "
+                                 f"sequence {b} and a source page of sequence {read[p]}")
+            if p in written:
+                raise ValueError(f"check_repage_tables: page {p} is a destination page twice: of "
+                                 f"sequence {written[p]} and of sequence {b} (page {j})")
+            written[p] = b
+
+
 def _resolve(method):
     if callable(method):
         return method
@@ -325,24 +531,33 @@ def _compress_paged(method, layers, out, kwargs):
         for i, d in enumerate(out):
             if d is None or (isinstance(d, str) and d == "inplace"):
                 dests.append("inplace")
+            elif isinstance(d, PagedDest):
+                dests.append(d)
             elif isinstance(d, (list, tuple)) and len(d) == 2:
                 dests.append(tuple(d))
             else:
-                raise TypeError(f"layer {i}: out entry must be a (K_dst, V_dst) pair or None")
+                raise TypeError(f"layer {i}: out entry must be a (K_dst, V_dst) pair, a "
+                                "PagedDest or None")
     else:
         raise TypeError(f"out must be \"inplace\" or a list, got {type(out).__name__}")
     if any(pk.ragged for pk in layers):
-        if any(d != "inplace" and pk.scaled for pk, d in zip(layers, dests)):
+        if any(isinstance(d, tuple) and pk.scaled for pk, d in zip(layers, dests)):
             raise TypeError("compress_paged: a scaled layer (k_scale / v_scale) is compacted in "
-                            "place only")
+                            "place or into a PagedDest only")
         return _compress_ragged(fn, layers, dests, kwargs)
     kvl = [_stand_in(pk) for pk in layers]
     seen = {}
+    pdests = [None] * L  # the bound PagedDest of a layer that has one
     for i, (pk, (k, v), d) in enumerate(zip(layers, kvl, dests)):  # before anything is enqueued
+        if isinstance(d, PagedDest):
+            # the deferred-call machinery carries a dense stand-in pair as the destination
+            pdests[i] = d.bind(i, pk)
+            dests[i] = pdests[i].stand_in(pk)
+            continue
         if d != "inplace" and pk.scaled:
             raise TypeError(f"layer {i}: a scaled layer (k_scale / v_scale) is compacted in "
-                            "place only: a dense out= pair has no channel for the kept rows' "
-                            "scales")
+                            "place or into a PagedDest only: a dense out= pair has no channel "
+                            "for the kept rows' scales")
         if d != "inplace":
             E._check_dest_tensors(i, k, v, d[0], d[1])
             continue
@@ -369,10 +584,20 @@ def _compress_paged(method, layers, out, kwargs):
                 raise RuntimeError(f"layer {j.layer_idx}: the method built a job that "
                                    "compress_paged cannot map onto its PagedKV")
             j.paged = pk
-            E._check_dest(j)
+            j.page_dest = pdests[j.layer_idx]
+            if j.page_dest is not None and \
+                    j.sink_len + j.n_select + j.tail_len > j.page_dest.capacity:
+                raise ValueError(
+                    f"layer {j.layer_idx}: PagedDest block_table "
+                    f"{tuple(j.page_dest.block_table.shape)} holds fewer than the "
+                    f"{-(-(j.sink_len + j.n_select + j.tail_len) // j.page_dest.page_size)} pages "
+                    f"of {j.sink_len + j.n_select + j.tail_len} rows of "
+                    f"{j.page_dest.page_size}")
+            if j.page_dest is None:  # (a PagedDest's stand-ins say nothing about memory)
+                E._check_dest(j)
             j.dest_verified = True
             E._check_tensors(j)
-            if j.k_dest is not j.keys:  # a dense destination must not meet the pools
+            if j.page_dest is None and j.k_dest is not j.keys:  # dense: must not meet the pools
                 n = j.sink_len + j.n_select + j.tail_len
                 for name, dst in (("K", j.k_dest), ("V", j.v_dest)):
                     lo, hi = E._span(dst, n)
@@ -395,13 +620,15 @@ def _compress_paged(method, layers, out, kwargs):
     for i, d in enumerate(dests):
         if d == "inplace":
             result.append(n_of[i] if i in n_of else int(res[i][0].size(2)))
+        elif pdests[i] is not None:  # the destination table now describes n rows
+            result.append(n_of.get(i, 0))
         else:
             n = n_of.get(i, 0)
             result.append((d[0].narrow(2, 0, n), d[1].narrow(2, 0, n)))
     return result
 
 
-def plan_ragged(fn, lens, geometry, kwargs, check=True):
+def plan_ragged(fn, lens, geometry, kwargs, check=True, unordered=()):
     """Host planning of a ragged call (no launch, no device copy): the method's own Python runs
     once per distinct per-layer length profile over B = 1 stand-ins, inside the deferred-call
     context, and every job or move it records becomes the kvc_seq_t record of its (layer,
@@ -409,13 +636,14 @@ def plan_ragged(fn, lens, geometry, kwargs, check=True):
     stand-ins; check=False skips the engine's tensor checks (host-only models of the mapping).
     Returns (records [L][B] SEQ_DTYPE, no-op where nothing moves; how: {(layer, b): (order, algo)
     of an engine job, or None for a copy-only move}; new lengths [L][B])."""
-    rec, spans, new_len = _plan_spans(fn, lens, geometry, kwargs, check)
+    rec, spans, new_len = _plan_spans(fn, lens, geometry, kwargs, check, unordered)
     return rec, {(li, b): how for li, bs, how in spans for b in bs}, new_len
 
 
-def _plan_spans(fn, lens, geometry, kwargs, check):
+def _plan_spans(fn, lens, geometry, kwargs, check, unordered=()):
     """plan_ragged with `how` per span: [(layer, [b, ...], (order, algo) | None)], one entry per
-    (profile, layer) that an engine job or a move touches."""
+    (profile, layer) that an engine job or a move touches.  `unordered`: the layers that are
+    written out of place (a PagedDest), which the in-place segment-order rule does not bind."""
     L, B = len(lens), len(lens[0])
     rec = np.zeros((L, B), dtype=N.SEQ_DTYPE)
     for li in range(L):  # the no-op record: every row a sink row
@@ -460,7 +688,8 @@ def _plan_spans(fn, lens, geometry, kwargs, check):
                         "caller-provided indices (strategy=\"random\", h2o_attention's heavy "
                         "hitters): compress such sequences one by one")
                 done.add(li)
-                E._check_dest(j)  # in place on a stand-in: the segment order
+                if li not in unordered:
+                    E._check_dest(j)  # in place on a stand-in: the segment order
                 if check:
                     E._check_tensors(j)
                 n = j.sink_len + j.n_select + j.tail_len
@@ -489,9 +718,10 @@ def _compress_ragged(fn, layers, dests, kwargs):
     group's launch every (layer, sequence) that belongs to another group -- or to none -- has the
     no-op record."""
     L = len(layers)
-    if any(d != "inplace" for d in dests):
+    if any(isinstance(d, tuple) for d in dests):
         raise TypeError("compress_paged: ragged layers (per-sequence lengths) are compacted in "
-                        "place only; dense out= pairs are not supported")
+                        "place only, or delivered to a PagedDest; dense out= pairs are not "
+                        "supported")
     if kwargs.get("strategy") == "random":
         raise TypeError("compress_paged: ragged layers (per-sequence lengths) do not take "
                         "caller-provided indices (strategy=\"random\")")
@@ -501,27 +731,49 @@ def _compress_ragged(fn, layers, dests, kwargs):
         if pk.block_table.size(0) != B:
             raise ValueError(f"layer {i}: {pk.block_table.size(0)} sequences, layer 0 has {B}: the "
                              "layers of a ragged call share one batch")
+        if isinstance(dests[i], PagedDest):  # the pool is only read
+            continue
         for name, t in (("K", pk.k_pool), ("V", pk.v_pool)):
             if t.data_ptr() in seen:
                 raise ValueError(f"layer {i}: {name} pool shares its memory with "
                                  f"{seen[t.data_ptr()]}: not compacted in place")
             seen[t.data_ptr()] = f"layer {i}'s {name} pool"
+    pdests = [d.bind(i, pk) if isinstance(d, PagedDest) else None
+              for i, (pk, d) in enumerate(zip(layers, dests))]
     rec, spans, new_len = _plan_spans(
         fn, [pk.seq_lens for pk in layers],
         [(pk.k_pool.size(1), pk.k_pool.size(3), pk.k_pool.dtype, pk.k_pool.device)
-         for pk in layers], kwargs, True)
+         for pk in layers], kwargs, True, {i for i, d in enumerate(pdests) if d is not None})
+    for li, pd in enumerate(pdests):
+        if pd is None:
+            continue
+        n = max(new_len[li], default=0)
+        if n > pd.capacity:
+            raise ValueError(f"layer {li}: PagedDest block_table {tuple(pd.block_table.shape)} "
+                             f"holds fewer than the {-(-n // pd.page_size)} pages of {n} rows of "
+                             f"{pd.page_size}")
+        # a sequence that no job or move touches passes through (or is already its front view):
+        # its destination table must describe it, so its rows are copied
+        rest = sorted(set(range(B)) - {b for l2, bs, _ in spans if l2 == li for b in bs})
+        rest = [b for b in rest if new_len[li][b] > 0]
+        if rest:
+            for b in rest:
+                rec[li, b] = (layers[li].seq_lens[b], 0, 0, 0, new_len[li][b], 0, 0,
+                              N.KVC_SCORE_NORM, 0, new_len[li][b], (0, 0))
+            spans.append((li, rest, None))
     # launch groups: engine jobs by their (order, algo); copy-only moves ride in a group of their
     # geometry (any order / algo: nothing is selected)
     # (scaled layers launch apart: kvc_launch_scaled takes a scale description per layer)
+    # (layers with a PagedDest launch apart as well: kvc_launch_repage)
     geos = [(pk.k_pool.get_device(), pk.k_pool.dtype, pk.k_pool.size(1), pk.k_pool.size(3),
-             pk.scaled) for pk in layers]
+             pk.scaled, pd is not None) for pk, pd in zip(layers, pdests)]
     groups = {}
     for li, bs, how in spans:
         if how is not None:
             groups.setdefault(geos[li] + how, {}).setdefault(li, []).extend(bs)
     for li, bs, how in spans:
         if how is None:
-            key = next((k for k in groups if k[:5] == geos[li]),
+            key = next((k for k in groups if k[:6] == geos[li]),
                        geos[li] + (N.KVC_ASC, N.KVC_ALGO_SORT))
             groups.setdefault(key, {}).setdefault(li, []).extend(bs)
     if not groups:
@@ -532,7 +784,9 @@ def _compress_ragged(fn, layers, dests, kwargs):
         lis = sorted(members)
         seqs = np.zeros((len(lis), B), dtype=N.SEQ_DTYPE)
         for i, li in enumerate(lis):
-            seqs[i]["seq_len"] = seqs[i]["sink_len"] = seqs[i]["n_out"] = layers[li].seq_lens
+            seqs[i]["seq_len"] = layers[li].seq_lens
+            if not key[5]:  # in place: the no-op record.  (A PagedDest layer: n_out = 0, nothing
+                seqs[i]["sink_len"] = seqs[i]["n_out"] = layers[li].seq_lens  # is written)
             seqs[i, members[li]] = rec[li, members[li]]
         per_dev.setdefault(key[0], []).append(seqs)
         plans.append((key, lis, len(per_dev[key[0]]) - 1))
@@ -543,7 +797,7 @@ def _compress_ragged(fn, layers, dests, kwargs):
         dev[device] = torch.from_numpy(host[device].view(np.uint8)).to(
             torch.device("cuda", device))
     launches = []
-    for (device, dtype, H, D, sc, order, algo), lis, slot in plans:  # plan (and check) every group
+    for (device, dtype, H, D, sc, repage, order, algo), lis, slot in plans:  # plan (and check)
         with torch.cuda.device(device):
             p = E._params(dtype, B, H, D, order, algo, False)
             n = len(lis)
@@ -551,6 +805,8 @@ def _compress_ragged(fn, layers, dests, kwargs):
             pages = np.zeros(n, dtype=N.PAGES_DTYPE)
             ragged = np.zeros(n, dtype=N.RAGGED_DTYPE)
             scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
+            pds = np.zeros(n, dtype=N.PAGE_DEST_DTYPE) if repage else None
+            dscales = np.zeros(n, dtype=N.SCALES_DTYPE) if repage and sc else None
             off = int(start[device][slot])
             for i, li in enumerate(lis):
                 pk = layers[li]
@@ -561,17 +817,24 @@ def _compress_ragged(fn, layers, dests, kwargs):
                 t["k_stride"] = (0, kp.stride(1), kp.stride(2))
                 t["v_stride"] = (0, vp.stride(1), vp.stride(2))
                 pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
-                            kp.size(0), 1, 0)
+                            kp.size(0), 0 if repage else 1, 0)
                 step = off + i * B * N.SEQ_DTYPE.itemsize
                 ragged[i] = (host[device].ctypes.data + step, dev[device].data_ptr() + step)
                 if sc:
                     scales[i] = pk.scales_row()
-            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged, scales)
-            launches.append((device, p, table, ws, info, pages, ragged, scales))
-    for device, p, table, ws, info, pages, ragged, scales in launches:
+                if repage:
+                    pd = pdests[li]
+                    t["k_out"], t["v_out"] = pd.k_pool.data_ptr(), pd.v_pool.data_ptr()
+                    pds[i] = pd.dest_row()
+                    if sc:
+                        dscales[i] = pd.scales_row(scales[i])
+            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged, scales, pds,
+                                 dscales)
+            launches.append((device, p, table, ws, info, pages, ragged, scales, pds, dscales))
+    for device, p, table, ws, info, pages, ragged, scales, pds, dscales in launches:
         with torch.cuda.device(device):
             E._launch(p, table, ws, info, torch.cuda.current_stream(device), p.phases, None, pages,
-                      ragged, scales)
+                      ragged, scales, pds, dscales)
     return new_len
 
 
@@ -581,9 +844,9 @@ def run_jobs(jobs, order, algo):
     groups = {}
     for j in jobs:
         B, H, _, D = j.paged.shape
-        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D, j.paged.scaled),
-                          []).append(j)
-    for (device, dtype, B, H, D, sc), js in groups.items():
+        groups.setdefault((j.keys.get_device(), j.keys.dtype, B, H, D, j.paged.scaled,
+                           j.page_dest is not None), []).append(j)
+    for (device, dtype, B, H, D, sc, repage), js in groups.items():
         external = any(j.ext_index is not None for j in js)
         if external and not all(j.ext_index is not None or j.n_select == 0 for j in js):
             raise RuntimeError("mixed external / engine-selected layers in one group")
@@ -595,6 +858,8 @@ def run_jobs(jobs, order, algo):
             pages = np.zeros(n, dtype=N.PAGES_DTYPE)
             dests = np.zeros(n, dtype=N.DEST_DTYPE)
             scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
+            pdests = np.zeros(n, dtype=N.PAGE_DEST_DTYPE) if repage else None
+            dscales = np.zeros(n, dtype=N.SCALES_DTYPE) if repage and sc else None
             dense = False
             for i, j in enumerate(js):
                 pk = j.paged
@@ -611,18 +876,26 @@ def run_jobs(jobs, order, algo):
                 pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
                             kp.size(0), 1 if inplace else 0, 0)
                 if sc:
-                    if not inplace:  # (compress_paged refuses it before anything is planned)
+                    if not inplace and not repage:  # (compress_paged refuses it before planning)
                         raise TypeError("a scaled layer is compacted in place only")
                     scales[i] = pk.scales_row()
-                if inplace:
+                if repage:  # through the destination table: kvc_launch_repage
+                    pd = j.page_dest
+                    t["k_out"], t["v_out"] = pd.k_pool.data_ptr(), pd.v_pool.data_ptr()
+                    pdests[i] = pd.dest_row()
+                    if sc:
+                        dscales[i] = pd.scales_row(scales[i])
+                elif inplace:
                     t["k_out"], t["v_out"] = t["k"], t["v"]
                 else:
                     dense = True
                     t["k_out"], t["v_out"] = j.k_dest.data_ptr(), j.v_dest.data_ptr()
                     dests[i] = (j.k_dest.stride()[:3], j.v_dest.stride()[:3], 0, 0)
             dd = dests if dense else None
-            ws, info = E._upload(p, table, device, js, B, H, dd, pages, None, scales)
-            E._launch(p, table, ws, info, stream, p.phases, dd, pages, None, scales)
+            ws, info = E._upload(p, table, device, js, B, H, dd, pages, None, scales, pdests,
+                                 dscales)
+            E._launch(p, table, ws, info, stream, p.phases, dd, pages, None, scales, pdests,
+                      dscales)
 
 
-__all__ = ["PagedKV", "compress_paged"]
+__all__ = ["PagedKV", "PagedDest", "compress_paged", "check_repage_tables"]

@@ -524,6 +524,102 @@ int kvc_launch_scaled(const kvc_params_t* params, const kvc_layer_t* layers,
                       const kvc_scales_t* scales, int num_layers, void* workspace,
                       size_t workspace_bytes, kvc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Paged destinations: pages to pages (additive within ABI 4: no existing struct, size or entry
+ * changes; a library without these two entries does not export them).
+ *
+ * Compaction in place (mode (c) of "Paged caches") asks the caller to promise that no written page
+ * is shared.  A server with prefix caching or forked sequences cannot: a shared prompt lies inside
+ * every method's scored zone.  With a kvc_page_dest_t per layer the compressed sequence of a paged
+ * layer is written through a SECOND block table into pages the caller chose -- fresh pages of the
+ * same pool (k_out == k, v_out == v) or another pool -- and the source pool is only read.
+ *
+ * Row addressing.  The layer's k_out / v_out are the DESTINATION pool bases (page 0); they may
+ * equal k / v.  Output row t in [0, n_out) of (b, h) is written at
+ *     k_out + (block_table[b * table_stride + (t >> log2 Pd)] * k_page_stride + h * k_stride[0]
+ *              + (t & (Pd - 1)) * k_stride[1]) * element size        (Pd = this page_size)
+ * and V likewise, with the table, page size, pool size and strides of THIS struct: none of them
+ * need equal the source's.  That includes the sink rows: nothing is "already in place".  Every
+ * other byte of every pool keeps its contents, destination rows [n_out, ...) of a partly filled
+ * page included.  Values are byte-identical to kvc_launch_paged into a dense destination for the
+ * same source table (torch.gather's NaN rewrite on the gathered segment only, none on fp8 bytes).
+ *
+ * Rules.  Every layer of the call is paged and pages[i].in_place is 0 (KVC_E_ARG).  There is no
+ * segment-order rule: out of place, any row map that is legal for a dense destination is legal
+ * here (ragged records included).  The destination pointers and strides obey the source pool's
+ * alignment rules (16-byte aligned k_out / v_out; head stride when heads > 1, slot stride when
+ * Pd > 1 and n_out > 1, page stride when num_pages > 1 multiples of 16 bytes: KVC_E_ALIGN).
+ * KVC_E_ARG: page_size not a power of two in [1, 65536]; num_pages < 1; table_stride smaller than
+ * ceil(n_out / page_size) (ragged: of the envelope's n_out, the largest record's); a zero stride
+ * on one of those dims larger than 1 (different rows would be one address); block_table NULL or
+ * not 4-byte aligned.  Layers with n_out == 0 are exempt.
+ *
+ * The caller's promise (the tables are device data: the library cannot check it without reading
+ * device memory, and it does not).  Within a call, a destination page that receives a row is
+ * none of: a source page that any sequence of that layer reads; a destination page of another
+ * (layer, b); a page of the other side (K / V).  The page ids of one destination table row are
+ * distinct.  Neither table is modified while the call runs.
+ *
+ * Ragged (ragged != NULL): per-sequence bounds come from the device records, as with
+ * kvc_launch_ragged; the records need not obey the in-place row-map rule.  On THIS path the old
+ * no-op record no longer means "nothing moves": a record with sink_len = n_out = seq_len (a
+ * sequence that passes through) is COPIED to its destination pages, because its destination table
+ * must describe it afterwards.  A record with n_out == 0 writes nothing: it stands for a sequence
+ * that belongs to another launch group.  A device record's n_out is capped at the planned
+ * envelope's.
+ *
+ * Scales (scales != NULL; fp8): dscales[i] describes the DESTINATION scale pools, addressed by the
+ * destination table and page size as the rows are.  For each side that is per-token in scales[i],
+ * dscales[i] must be per-token too, with a non-NULL (KVC_E_ARG), 4-byte aligned (KVC_E_ALIGN)
+ * pointer and non-zero strides on every dim larger than 1 (pages when the destination's
+ * num_pages > 1, heads, slots when Pd > 1; KVC_E_ARG); the 4 bytes of source row src(t)'s scale
+ * are stored at output row t's slot, uninterpreted (a NaN keeps its payload).  A side that is
+ * uniform or absent in scales[i] moves nothing, and dscales[i] must carry the same flag on that
+ * side (KVC_E_ARG); its pointer is not read.  dscales == NULL with scales != NULL is KVC_E_ARG.
+ * SCORE reads the SOURCE scales as kvc_launch_scaled does.
+ *
+ * Device safety: a destination page id outside [0, num_pages) drops that row's stores, its scale
+ * stores included, and sets KVC_DEV_INDEX_RANGE; a bad source id is clamped for loads, as on
+ * every paged path.
+ *
+ * SCORE and SELECT are the kernels of kvc_launch_paged / _ragged / _scaled, unchanged; GATHER is a
+ * copy kernel of its own on the out-of-place grid (rows, passes of the longest output), for
+ * ragged layers too (a block past its sequence's n_out returns after the record load).  Phases
+ * may be launched separately.  external_index and KVC_FLAG_SHARED_INDEX work when ragged == NULL;
+ * KVC_FLAG_GATHER_FIXED / _SELECTED are refused (KVC_E_ARG).  Plan info and workspace layout are
+ * those of the in-place call for the same tables.  Both tables (and the ragged records) are read
+ * when the kernels run: a replay of a captured launch follows their contents at replay time.
+ * Kernel arguments travel by value: chunks of 32 layers, of 16 when scales move (two scale
+ * descriptions per layer would take 32 layers past 12 KiB of arguments).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct kvc_page_dest {
+  const int32_t* block_table; /* device: DESTINATION page id of logical page p of row b at
+                                 block_table[b * table_stride + p]                            */
+  int64_t table_stride;       /* >= ceil(n_out / page_size) (ragged: of the largest n_out)    */
+  int64_t k_page_stride;      /* elements between consecutive pages of the destination K pool */
+  int64_t v_page_stride;
+  int64_t k_stride[2];        /* element strides of the heads and of the slots inside a page  */
+  int64_t v_stride[2];
+  int32_t page_size;          /* power of two in [1, 65536]; need not equal the source's      */
+  int32_t num_pages;          /* pages in the destination pool, >= 1                          */
+} kvc_page_dest_t;            /* 72 bytes */
+
+/* kvc_plan_scaled with paged destinations: pdests[i] (and dscales[i]) belong to layers[i].
+ * ragged, scales and dscales are nullable as in the entries above; pdests == NULL behaves exactly
+ * like kvc_plan_scaled.  Fills the same layer fields and kvc_plan_info_t.  Pure host function. */
+int kvc_plan_repage(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
+                    const kvc_ragged_t* ragged, const kvc_scales_t* scales,
+                    const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int num_layers,
+                    kvc_plan_info_t* info);
+
+/* kvc_launch_scaled with paged destinations (pdests == NULL: exactly kvc_launch_scaled).
+ * Re-validates as kvc_plan_repage does; the kernels receive every table by value. */
+int kvc_launch_repage(const kvc_params_t* params, const kvc_layer_t* layers,
+                      const kvc_pages_t* pages, const kvc_ragged_t* ragged,
+                      const kvc_scales_t* scales, const kvc_page_dest_t* pdests,
+                      const kvc_scales_t* dscales, int num_layers, void* workspace,
+                      size_t workspace_bytes, kvc_stream_t stream);
+
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |
  * KVC_PHASE_GATHER) kernel of a planned table (at most 64 layers) as kvc_launch would, but with

@@ -21,6 +21,16 @@ GPU box only.
   c_uniform         the headline call as a list of equal lengths (ragged kernels) and as an int
                     (the existing kernels): the price of the record indirection;
   d_host_planning   host planning time against the number of distinct length profiles.
+--repage measures paged DESTINATIONS (kvc_launch_repage; DESIGN.md, "Paged destinations"), P = 16,
+pools stored [N, P, H, D], in three alternating rounds of all four configurations (one JSON line
+per round and configuration, so the spread is visible):
+  a_inplace          the headline call compacted in place (the existing kernels);
+  b_fresh_pages      the same call into fresh pages of the same pool (out=[PagedDest(table)]);
+  c_ragged_inplace / c_ragged_fresh   the ragged profile of --ragged (B = 8, lengths 600 .. 16 384,
+                     8 heads), in place against into fresh pages.
+The figure to watch is `gpu_ms_gather` of b against a (and of c_ragged_fresh against
+c_ragged_inplace): the out-of-place copy moves the same bytes plus the sink rows, with its passes
+side by side instead of one workgroup per row.
 `ms_call` is event to event around whole calls (host-bound when the GPU is idle between
 launches), `gpu_ms*` the summed kernel durations of a call's launches, `host_us` the enqueue time.
 """
@@ -225,6 +235,68 @@ def ragged_main(args):
                 f.write(json.dumps(ln) + "\n")
 
 
+# ---- --repage: pages to pages ("Paged destinations") ---------------------------------
+def repage_main(args):
+    from kvcompress import PagedDest
+    L, P, gen = args.layers, 16, torch.Generator(device=DEV).manual_seed(0)
+    keep = KW["fix_kv_size"]
+    lines = []
+
+    def pools(lens, heads):
+        """L layers: nphd pool pair with room for the sources, `keep` fresh rows per sequence and
+        the spare pages; the source table and the table of the fresh pages."""
+        npp = [-(-n // P) for n in lens]
+        fresh = -(-keep // P)
+        n = sum(npp) + len(lens) * fresh + SPARE
+        out = []
+        for _ in range(L):
+            kv = [torch.empty(n, P, heads, D, dtype=torch.bfloat16, device=DEV)
+                  .normal_(generator=gen).permute(0, 2, 1, 3) for _ in range(2)]
+            perm = torch.randperm(n, generator=gen, device=DEV).to(torch.int32)
+            src = torch.zeros(len(lens), max(npp), dtype=torch.int32, device=DEV)
+            at = 0
+            for b, c in enumerate(npp):
+                src[b, :c] = perm[at:at + c]
+                at += c
+            dst = perm[at:at + len(lens) * fresh].reshape(len(lens), fresh).contiguous()
+            out.append((kv[0], kv[1], src, dst))
+        return out
+
+    configs, hold = {}, []
+    for name, lens, heads, ragged in (("headline", [SHAPES["headline"]], H, False),
+                                      ("ragged", spread(8), 8, True)):
+        for fresh in (False, True):
+            ps = pools(lens, heads)  # a pool set per configuration: in place rewrites its own
+            hold.append(ps)
+            layers = [PagedKV(k, v, t, list(lens) if ragged else lens[0]) for k, v, t, _ in ps]
+            out = [PagedDest(d) for _, _, _, d in ps] if fresh else "inplace"
+            key = ("c_ragged_" + ("fresh" if fresh else "inplace")) if ragged else \
+                ("b_fresh_pages" if fresh else "a_inplace")
+            configs[key] = (lambda layers=layers, out=out: compress_paged(METHOD, layers, out=out,
+                                                                          **KW),
+                            dict(B=len(lens), H=heads, tokens=sum(lens)))
+    for fn, _ in configs.values():  # warm-up
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    reps = 4
+    for rnd in range(3):
+        for key in sorted(configs):
+            fn, info = configs[key]
+            ms = sample(fn, reps)
+            g = gpu_ms(fn, reps)
+            lines.append(dict(tool="paged_bench", mode="repage", method=METHOD, layers=L,
+                              page_size=P, storage="nphd", dtype="bf16", D=D, config=key,
+                              round=rnd, ms_call=round(ms, 4), gpu_ms_score=g.get("score", 0.0),
+                              gpu_ms_select=g.get("select", 0.0),
+                              gpu_ms_gather=g.get("gather", 0.0), reps=reps, **info))
+            print(json.dumps(lines[-1]), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="headline,decode")
@@ -233,9 +305,13 @@ def main():
     ap.add_argument("--out", default="", help="append the JSON lines to this file as well")
     ap.add_argument("--ragged", action="store_true",
                     help="measure ragged batches (per-sequence lengths) instead of the shapes")
+    ap.add_argument("--repage", action="store_true",
+                    help="measure paged destinations (pages to pages) against in place")
     args = ap.parse_args()
     if args.ragged:
         return ragged_main(args)
+    if args.repage:
+        return repage_main(args)
     L = args.layers
     gen = torch.Generator(device=DEV).manual_seed(0)
     dense_fn = get_compress_fn(METHOD)
