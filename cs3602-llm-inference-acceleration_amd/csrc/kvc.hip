@@ -234,62 +234,38 @@ static bool in_place_row_map_ok(const kvc_layer_t& y) {
                                y.sink_len > y.tail_start)));
 }
 
-// kvc_plan_dest / kvc_launch_dest: plan_impl, then the destinations of every layer with output
-// (include/kvc.h, "Caller-provided destinations").  dests == nullptr: plan_impl alone.
-static int plan_dest_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_dest_t* dests,
-                          int nl, kvc_plan_info_t* info, bool fill) {
-  int rc = plan_impl(p, layers, nl, info, fill);
-  if (rc != KVC_OK || !dests) return rc;
-  if (p->flags & (KVC_FLAG_GATHER_FIXED | KVC_FLAG_GATHER_SELECTED)) return KVC_E_ARG;
-  const int es = esize(p->dtype);
-  const int64_t rowb = (int64_t)p->head_dim * es;
-  const int64_t B = p->batch, H = p->heads;
-  for (int l = 0; l < nl; ++l) {
-    const kvc_layer_t& y = layers[l];
-    const kvc_dest_t& d = dests[l];
-    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
-    if (n_out == 0) continue;
-    if (d.reserved != 0 || (d.in_place != 0 && d.in_place != 1)) return KVC_E_ARG;
-    if (!dest_strides_aligned(d, B, H, n_out, es)) return KVC_E_ALIGN;
-    const int64_t* ks = d.k_stride;
-    const int64_t* vs = d.v_stride;
-    if (d.in_place) {
-      if (y.k_out != y.k || y.v_out != y.v || memcmp(ks, y.k_stride, sizeof(y.k_stride)) ||
-          memcmp(vs, y.v_stride, sizeof(y.v_stride)))
-        return KVC_E_ARG;
-      if (!in_place_row_map_ok(y)) return KVC_E_ARG;
-      // a zero stride (an expanded batch) would be written twice
-      if ((B > 1 && (ks[0] == 0 || vs[0] == 0)) || (H > 1 && (ks[1] == 0 || vs[1] == 0)) ||
-          (y.seq_len > 1 && (ks[2] == 0 || vs[2] == 0)))
-        return KVC_E_ARG;
-    } else {
-      const int64_t ssize[3] = {B, H, y.seq_len}, dsize[3] = {B, H, n_out};
-      const Span src[2] = {span(y.k, ssize, y.k_stride, es, rowb),
-                           span(y.v, ssize, y.v_stride, es, rowb)};
-      const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
-                           span(y.v_out, dsize, d.v_stride, es, rowb)};
-      if (ranges_meet(dst, src)) return KVC_E_ARG;
-    }
-  }
-  return KVC_OK;
+// The optional tables of one call, as its entry point received them (include/kvc.h): a null
+// member means the call has no such table.  pdests != nullptr is "GATHER writes through
+// destination block tables" (kvc_plan_repage / kvc_launch_repage): such a call is out of place.
+struct Tables {
+  const kvc_dest_t* dests;
+  const kvc_pages_t* pages;
+  const kvc_ragged_t* ragged;
+  const kvc_scales_t* scales;
+  const kvc_page_dest_t* pdests;
+  const kvc_scales_t* dscales;  // with scales and pdests only
+};
+
+// A block table over a pool of num_pages pages of page_size slots that holds `rows` logical rows:
+// the geometry of a source (kvc_pages_t) or a destination (kvc_page_dest_t) description.
+static bool page_geometry_ok(const int32_t* table, int64_t table_stride, int num_pages,
+                             int page_size, int64_t rows) {
+  if (!table || ((uintptr_t)table & 3u) || num_pages < 1 || page_size < 1 || page_size > 65536 ||
+      (page_size & (page_size - 1)))
+    return false;
+  return table_stride >= (rows + page_size - 1) / page_size;
 }
 
-// kvc_plan_paged / kvc_launch_paged: plan_impl, then the page description (and the dense
-// destination, if any) of every layer with output (include/kvc.h, "Paged caches").
-// pages == nullptr: plan_dest_impl.
-// The page description of one layer with output, and what compaction in place asks of it.
-// row_map: apply the in-place row-map rule to y's segments (a ragged layer's rule is checked per
-// record, and y holds their envelope).
+// The page description of one layer with output, and what compaction in place asks of it
+// (include/kvc.h, "Paged caches").  row_map: apply the in-place row-map rule to y's segments (a
+// ragged layer's rule is checked per record, and y holds their envelope).
 static int paged_layer_check(const kvc_params_t* p, const kvc_layer_t& y, const kvc_pages_t& g,
                              bool row_map) {
   const int es = esize(p->dtype);
-  const int64_t H = p->heads;
-  if (!g.block_table || ((uintptr_t)g.block_table & 3u) || g.reserved != 0 ||
-      (g.in_place != 0 && g.in_place != 1) || g.num_pages < 1 || g.page_size < 1 ||
-      g.page_size > 65536 || (g.page_size & (g.page_size - 1)))
+  const int64_t H = p->heads, P = g.page_size;
+  if (g.reserved != 0 || (g.in_place != 0 && g.in_place != 1) ||
+      !page_geometry_ok(g.block_table, g.table_stride, g.num_pages, g.page_size, y.seq_len))
     return KVC_E_ARG;
-  const int64_t P = g.page_size;
-  if (g.table_stride < ((int64_t)y.seq_len + P - 1) / P) return KVC_E_ARG;
   if (y.k_stride[0] != 0 || y.v_stride[0] != 0) return KVC_E_ARG;  // the table is the batch dim
   // (plan_impl has checked the head and slot strides against heads > 1 / seq_len > 1)
   if (g.num_pages > 1 && ((g.k_page_stride * es) % 16 || (g.v_page_stride * es) % 16))
@@ -306,58 +282,61 @@ static int paged_layer_check(const kvc_params_t* p, const kvc_layer_t& y, const 
   return KVC_OK;
 }
 
-static int plan_paged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
-                           const kvc_dest_t* dests, int nl, kvc_plan_info_t* info, bool fill) {
-  if (!pages) return plan_dest_impl(p, layers, dests, nl, info, fill);
-  int rc = plan_impl(p, layers, nl, info, fill);
-  if (rc != KVC_OK) return rc;
-  if (p->flags & (KVC_FLAG_GATHER_FIXED | KVC_FLAG_GATHER_SELECTED)) return KVC_E_ARG;
+// The dense destination of one layer with output (include/kvc.h, "Caller-provided
+// destinations"): of a [B, H, S, D] source view or -- g != nullptr -- of the layer's page pools,
+// which a dense destination never compacts in place (that is kvc_pages_t.in_place).
+static int dest_layer_check(const kvc_params_t* p, const kvc_layer_t& y, const kvc_dest_t& d,
+                            const kvc_pages_t* g) {
   const int es = esize(p->dtype);
   const int64_t rowb = (int64_t)p->head_dim * es;
-  const int64_t B = p->batch, H = p->heads;
-  for (int l = 0; l < nl; ++l) {
-    const kvc_layer_t& y = layers[l];
-    const kvc_pages_t& g = pages[l];
-    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
-    if (n_out == 0) continue;
-    rc = paged_layer_check(p, y, g, true);
-    if (rc != KVC_OK) return rc;
-    if (g.in_place) continue;
-    const int64_t P = g.page_size;
-    if (!dests) continue;  // contiguous k_out / v_out
-    const kvc_dest_t& d = dests[l];
-    if (d.reserved != 0 || d.in_place != 0) return KVC_E_ARG;
-    if (!dest_strides_aligned(d, B, H, n_out, es)) return KVC_E_ALIGN;
-    const int64_t psize[3] = {g.num_pages, H, P}, dsize[3] = {B, H, n_out};
-    const int64_t kst[3] = {g.k_page_stride, y.k_stride[1], y.k_stride[2]};
-    const int64_t vst[3] = {g.v_page_stride, y.v_stride[1], y.v_stride[2]};
-    const Span src[2] = {span(y.k, psize, kst, es, rowb), span(y.v, psize, vst, es, rowb)};
-    const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
-                         span(y.v_out, dsize, d.v_stride, es, rowb)};
-    if (ranges_meet(dst, src)) return KVC_E_ARG;
+  const int64_t B = p->batch, H = p->heads, n_out = y.n_out;
+  if (d.reserved != 0 || (d.in_place != 0 && (g || d.in_place != 1))) return KVC_E_ARG;
+  if (!dest_strides_aligned(d, B, H, n_out, es)) return KVC_E_ALIGN;
+  const int64_t* ks = d.k_stride;
+  const int64_t* vs = d.v_stride;
+  if (d.in_place) {
+    if (y.k_out != y.k || y.v_out != y.v || memcmp(ks, y.k_stride, sizeof(y.k_stride)) ||
+        memcmp(vs, y.v_stride, sizeof(y.v_stride)))
+      return KVC_E_ARG;
+    if (!in_place_row_map_ok(y)) return KVC_E_ARG;
+    // a zero stride (an expanded batch) would be written twice
+    if ((B > 1 && (ks[0] == 0 || vs[0] == 0)) || (H > 1 && (ks[1] == 0 || vs[1] == 0)) ||
+        (y.seq_len > 1 && (ks[2] == 0 || vs[2] == 0)))
+      return KVC_E_ARG;
+    return KVC_OK;
   }
-  return KVC_OK;
+  // the source's byte range: the view's, or the whole pools' (pages x heads x slots)
+  int64_t ssize[3] = {B, H, y.seq_len};
+  int64_t kst[3] = {y.k_stride[0], y.k_stride[1], y.k_stride[2]};
+  int64_t vst[3] = {y.v_stride[0], y.v_stride[1], y.v_stride[2]};
+  if (g) {
+    ssize[0] = g->num_pages, ssize[2] = g->page_size;
+    kst[0] = g->k_page_stride, vst[0] = g->v_page_stride;
+  }
+  const int64_t dsize[3] = {B, H, n_out};
+  const Span src[2] = {span(y.k, ssize, kst, es, rowb), span(y.v, ssize, vst, es, rowb)};
+  const Span dst[2] = {span(y.k_out, dsize, d.k_stride, es, rowb),
+                       span(y.v_out, dsize, d.v_stride, es, rowb)};
+  return ranges_meet(dst, src) ? KVC_E_ARG : KVC_OK;
 }
 
-// kvc_plan_ragged / kvc_launch_ragged (include/kvc.h, "Ragged paged batches"): every host record
-// under a layer's rules, the layers' segment fields set to (fill) or compared with (launch) the
-// envelope of their records, then plan_impl and the page checks on that envelope.
-// ragged == nullptr: plan_paged_impl without destinations.
-// repage (plan_repage_impl): the layers are written through a destination table, out of place --
-// in_place must be 0 and the records are free of the in-place row-map rule.
-static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
-                            const kvc_ragged_t* ragged, int nl, kvc_plan_info_t* info,
-                            bool fill, bool repage = false) {
-  if (!ragged) return plan_paged_impl(p, layers, pages, nullptr, nl, info, fill);
-  if (!p || nl < 0 || (nl > 0 && (!layers || !pages)) || p->batch < 1) return KVC_E_ARG;
+// The ragged step of plan_tables (include/kvc.h, "Ragged paged batches"): every host record under
+// a layer's rules, the layers' segment fields set to (fill) or compared with (launch) the envelope
+// of their records.  The records compact in place -- in_place must be 1, each record under the
+// in-place row-map rule -- unless the call writes through destination tables: then in_place must
+// be 0 and the records are free of that rule.
+static int ragged_envelopes(const kvc_params_t* p, kvc_layer_t* layers, const Tables& t, int nl,
+                            bool fill) {
+  const bool in_place = !t.pdests;
+  if (!p || nl < 0 || (nl > 0 && (!layers || !t.pages)) || p->batch < 1) return KVC_E_ARG;
   if (p->external_index || (p->flags & (KVC_FLAG_SHARED_INDEX | KVC_FLAG_GATHER_FIXED |
                                         KVC_FLAG_GATHER_SELECTED)))
     return KVC_E_ARG;
   for (int l = 0; l < nl; ++l) {
-    const kvc_ragged_t& r = ragged[l];
+    const kvc_ragged_t& r = t.ragged[l];
     if (!r.host || !r.dev || ((uintptr_t)r.host & 3u) || ((uintptr_t)r.dev & 15u))
       return KVC_E_ARG;
-    if (pages[l].in_place != (repage ? 0 : 1)) return KVC_E_ARG;
+    if (t.pages[l].in_place != (in_place ? 1 : 0)) return KVC_E_ARG;
     kvc_layer_t e = layers[l];  // the envelope
     e.seq_len = e.zone_start = e.zone_len = e.n_select = e.sink_len = e.tail_start = 0;
     e.tail_len = e.pool_kernel = 0;
@@ -377,7 +356,7 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
       kvc_layer_t y = e;  // the record as a layer: the row-map rule's argument
       y.zone_start = q.zone_start, y.zone_len = q.zone_len, y.n_select = q.n_select;
       y.sink_len = q.sink_len, y.tail_start = q.tail_start, y.tail_len = q.tail_len;
-      if (!repage && !in_place_row_map_ok(y)) return KVC_E_ARG;
+      if (in_place && !in_place_row_map_ok(y)) return KVC_E_ARG;
       const bool sel = layer_selects(y);
       selects |= sel;
       e.seq_len = S > e.seq_len ? S : e.seq_len;
@@ -404,131 +383,123 @@ static int plan_ragged_impl(const kvc_params_t* p, kvc_layer_t* layers, const kv
       return KVC_E_ARG;
     }
   }
-  int rc = plan_impl(p, layers, nl, info, fill);
-  if (rc != KVC_OK) return rc;
-  for (int l = 0; l < nl; ++l) {
-    if (layers[l].n_out == 0) continue;
-    rc = paged_layer_check(p, layers[l], pages[l], false);
-    if (rc != KVC_OK) return rc;
-  }
   return KVC_OK;
 }
 
-// kvc_plan_scaled / kvc_launch_scaled (include/kvc.h, "Per-token-scaled fp8 paged caches"):
-// plan_ragged_impl (ragged == nullptr: the single-length paged plan), then the scale description
-// of every layer.  scales == nullptr: plan_ragged_impl alone.
-static int plan_scaled_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
-                            const kvc_ragged_t* ragged, const kvc_scales_t* scales, int nl,
-                            kvc_plan_info_t* info, bool fill, bool repage = false) {
-  int rc = plan_ragged_impl(p, layers, pages, ragged, nl, info, fill, repage);
-  if (rc != KVC_OK || !scales) return rc;
-  if (nl > 0 && !pages) return KVC_E_ARG;  // every scaled layer is paged
-  if (!is_fp8(p->dtype)) return KVC_E_DTYPE;
-  constexpr int kKnown =
-      KVC_SCALE_K_UNIFORM | KVC_SCALE_V_UNIFORM | KVC_SCALE_K_NONE | KVC_SCALE_V_NONE;
-  for (int l = 0; l < nl; ++l) {
-    const kvc_scales_t& z = scales[l];
-    const kvc_pages_t& g = pages[l];
-    // a dense output has no channel for the moved scales (a paged destination has: dscales)
-    if (!repage &&
-        (g.in_place != 1 || layers[l].k_out != layers[l].k || layers[l].v_out != layers[l].v))
+// One kvc_scales_t (include/kvc.h, "Per-token-scaled fp8 paged caches") over pools of num_pages
+// pages of page_size slots: each side that is read has a pointer, 4-byte aligned, and -- where it
+// is a pool -- no zero stride over a dimension longer than one.  A uniform K scale is one word
+// that SCORE reads (k_uniform_read; GATHER moves no uniform word, so a destination's is not
+// read); a uniform V scale is never read: its pointer may be anything.
+static int scale_sides_check(const kvc_scales_t& z, bool k_uniform_read, int64_t num_pages,
+                             int64_t heads, int64_t page_size) {
+  const struct {
+    const float* ptr;
+    int64_t page, head, slot;
+    bool read, pool;
+  } side[2] = {
+      {z.k_scale, z.k_page_stride, z.k_stride[0], z.k_stride[1],
+       !(z.flags & (KVC_SCALE_K_NONE | (k_uniform_read ? 0 : KVC_SCALE_K_UNIFORM))),
+       !(z.flags & (KVC_SCALE_K_NONE | KVC_SCALE_K_UNIFORM))},
+      {z.v_scale, z.v_page_stride, z.v_stride[0], z.v_stride[1],
+       !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM)),
+       !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM))}};
+  for (const auto& s : side) {
+    if (!s.read) continue;
+    if (!s.ptr) return KVC_E_ARG;
+    if ((uintptr_t)s.ptr & 3u) return KVC_E_ALIGN;
+    // a zero stride would make the scales of different rows -- of different heads, each
+    // compacted by its own workgroup -- one word
+    if (s.pool && ((num_pages > 1 && s.page == 0) || (heads > 1 && s.head == 0) ||
+                   (page_size > 1 && s.slot == 0)))
       return KVC_E_ARG;
-    if ((z.flags & ~kKnown) || z.reserved != 0 ||
-        ((z.flags & KVC_SCALE_K_UNIFORM) && (z.flags & KVC_SCALE_K_NONE)) ||
-        ((z.flags & KVC_SCALE_V_UNIFORM) && (z.flags & KVC_SCALE_V_NONE)))
-      return KVC_E_ARG;
-    const struct {
-      const float* ptr;
-      int64_t page, head, slot;
-      bool read, pool;
-    } side[2] = {
-        {z.k_scale, z.k_page_stride, z.k_stride[0], z.k_stride[1], !(z.flags & KVC_SCALE_K_NONE),
-         !(z.flags & (KVC_SCALE_K_NONE | KVC_SCALE_K_UNIFORM))},
-        // (a uniform V scale is never read: its pointer may be anything)
-        {z.v_scale, z.v_page_stride, z.v_stride[0], z.v_stride[1],
-         !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM)),
-         !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM))}};
-    for (const auto& s : side) {
-      if (!s.read) continue;
-      if (!s.ptr) return KVC_E_ARG;
-      if ((uintptr_t)s.ptr & 3u) return KVC_E_ALIGN;
-      // a zero stride would make the scales of different rows -- of different heads, each
-      // compacted by its own workgroup -- one word
-      if (s.pool && ((g.num_pages > 1 && s.page == 0) || (p->heads > 1 && s.head == 0) ||
-                     (g.page_size > 1 && s.slot == 0)))
-        return KVC_E_ARG;
-    }
   }
   return KVC_OK;
 }
+constexpr int kScaleFlags =
+    KVC_SCALE_K_UNIFORM | KVC_SCALE_V_UNIFORM | KVC_SCALE_K_NONE | KVC_SCALE_V_NONE;
 
-// kvc_plan_repage / kvc_launch_repage (include/kvc.h, "Paged destinations"): plan_scaled_impl
-// without the in-place rules, then the destination description -- and, for scaled layers, the
-// destination scale pools -- of every layer with output.  pdests == nullptr: plan_scaled_impl.
-static int plan_repage_impl(const kvc_params_t* p, kvc_layer_t* layers, const kvc_pages_t* pages,
-                            const kvc_ragged_t* ragged, const kvc_scales_t* scales,
-                            const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int nl,
-                            kvc_plan_info_t* info, bool fill) {
-  if (!pdests) return plan_scaled_impl(p, layers, pages, ragged, scales, nl, info, fill);
-  if (nl > 0 && !pages) return KVC_E_ARG;  // every layer with a paged destination is paged
-  int rc = plan_scaled_impl(p, layers, pages, ragged, scales, nl, info, fill, true);
-  if (rc != KVC_OK) return rc;
-  if (scales && !dscales) return KVC_E_ARG;
+// The destination description of one layer with output (include/kvc.h, "Paged destinations");
+// y.n_out is a ragged layer's largest record's.
+static int page_dest_layer_check(const kvc_params_t* p, const kvc_layer_t& y,
+                                 const kvc_page_dest_t& d) {
   const int es = esize(p->dtype);
-  const int64_t H = p->heads;
-  constexpr int kKnown =
-      KVC_SCALE_K_UNIFORM | KVC_SCALE_V_UNIFORM | KVC_SCALE_K_NONE | KVC_SCALE_V_NONE;
-  for (int l = 0; l < nl; ++l) {
-    const kvc_layer_t& y = layers[l];  // (ragged: the envelope, n_out the largest record's)
-    const int64_t n_out = (int64_t)y.sink_len + y.n_select + y.tail_len;
-    if (n_out == 0) continue;
-    if (pages[l].in_place != 0) return KVC_E_ARG;
-    const kvc_page_dest_t& d = pdests[l];
-    if (!d.block_table || ((uintptr_t)d.block_table & 3u) || d.num_pages < 1 || d.page_size < 1 ||
-        d.page_size > 65536 || (d.page_size & (d.page_size - 1)))
-      return KVC_E_ARG;
-    const int64_t P = d.page_size;
-    if (d.table_stride < (n_out + P - 1) / P) return KVC_E_ARG;
-    const bool heads = H > 1, slots = P > 1 && n_out > 1, pgs = d.num_pages > 1;
-    // a zero stride would make different output rows one address
-    if ((heads && (d.k_stride[0] == 0 || d.v_stride[0] == 0)) ||
-        (slots && (d.k_stride[1] == 0 || d.v_stride[1] == 0)) ||
-        (pgs && (d.k_page_stride == 0 || d.v_page_stride == 0)))
-      return KVC_E_ARG;
-    // (plan_impl has checked k_out / v_out themselves)
-    if ((heads && ((d.k_stride[0] * es) % 16 || (d.v_stride[0] * es) % 16)) ||
-        (slots && ((d.k_stride[1] * es) % 16 || (d.v_stride[1] * es) % 16)) ||
-        (pgs && ((d.k_page_stride * es) % 16 || (d.v_page_stride * es) % 16)))
-      return KVC_E_ALIGN;
-    if (!scales) continue;
-    const kvc_scales_t& z = scales[l];
-    const kvc_scales_t& dz = dscales[l];
-    if ((dz.flags & ~kKnown) || dz.reserved != 0 || dz.flags != z.flags) return KVC_E_ARG;
-    const struct {
-      const float* ptr;
-      int64_t page, head, slot;
-      bool pool;
-    } side[2] = {{dz.k_scale, dz.k_page_stride, dz.k_stride[0], dz.k_stride[1],
-                  !(z.flags & (KVC_SCALE_K_NONE | KVC_SCALE_K_UNIFORM))},
-                 {dz.v_scale, dz.v_page_stride, dz.v_stride[0], dz.v_stride[1],
-                  !(z.flags & (KVC_SCALE_V_NONE | KVC_SCALE_V_UNIFORM))}};
-    for (const auto& s : side) {
-      if (!s.pool) continue;  // uniform or absent: nothing moves, the pointer is not read
-      if (!s.ptr) return KVC_E_ARG;
-      if ((uintptr_t)s.ptr & 3u) return KVC_E_ALIGN;
-      if ((pgs && s.page == 0) || (heads && s.head == 0) || (P > 1 && s.slot == 0))
+  if (!page_geometry_ok(d.block_table, d.table_stride, d.num_pages, d.page_size, y.n_out))
+    return KVC_E_ARG;
+  const bool heads = p->heads > 1, slots = d.page_size > 1 && y.n_out > 1, pgs = d.num_pages > 1;
+  // a zero stride would make different output rows one address
+  if ((heads && (d.k_stride[0] == 0 || d.v_stride[0] == 0)) ||
+      (slots && (d.k_stride[1] == 0 || d.v_stride[1] == 0)) ||
+      (pgs && (d.k_page_stride == 0 || d.v_page_stride == 0)))
+    return KVC_E_ARG;
+  // (plan_impl has checked k_out / v_out themselves)
+  if ((heads && ((d.k_stride[0] * es) % 16 || (d.v_stride[0] * es) % 16)) ||
+      (slots && ((d.k_stride[1] * es) % 16 || (d.v_stride[1] * es) % 16)) ||
+      (pgs && ((d.k_page_stride * es) % 16 || (d.v_page_stride * es) % 16)))
+    return KVC_E_ALIGN;
+  return KVC_OK;
+}
+
+// The plan of every entry point: plan_impl, and around it one step per table the call has, in
+// this order (the first fault found is the one reported).  fill: write the layers' planned
+// fields (kvc_plan*); otherwise compare them (kvc_launch*).
+static int plan_tables(const kvc_params_t* p, kvc_layer_t* layers, const Tables& t, int nl,
+                       kvc_plan_info_t* info, bool fill) {
+  if (t.pdests && nl > 0 && !t.pages) return KVC_E_ARG;  // a paged destination: a paged layer
+  int rc = t.ragged ? ragged_envelopes(p, layers, t, nl, fill) : KVC_OK;
+  if (rc != KVC_OK) return rc;
+  rc = plan_impl(p, layers, nl, info, fill);  // (ragged: on the envelopes)
+  if (rc != KVC_OK) return rc;
+  // pages, and dense destinations (never with pdests): layer by layer
+  if (t.pages || t.dests) {
+    if (p->flags & (KVC_FLAG_GATHER_FIXED | KVC_FLAG_GATHER_SELECTED)) return KVC_E_ARG;
+    for (int l = 0; l < nl; ++l) {
+      const kvc_layer_t& y = layers[l];
+      if (y.n_out == 0) continue;
+      const kvc_pages_t* g = t.pages ? &t.pages[l] : nullptr;
+      if (g && (rc = paged_layer_check(p, y, *g, !t.ragged)) != KVC_OK) return rc;
+      // (without dests, a layer that is not in place has a contiguous k_out / v_out)
+      if (t.dests && !(g && g->in_place) &&
+          (rc = dest_layer_check(p, y, t.dests[l], g)) != KVC_OK)
+        return rc;
+    }
+  }
+  if (t.scales) {
+    if (nl > 0 && !t.pages) return KVC_E_ARG;  // every scaled layer is paged
+    if (!is_fp8(p->dtype)) return KVC_E_DTYPE;
+    for (int l = 0; l < nl; ++l) {
+      const kvc_layer_t& y = layers[l];
+      const kvc_scales_t& z = t.scales[l];
+      const kvc_pages_t& g = t.pages[l];
+      // a dense output has no channel for the moved scales (a paged destination has: dscales)
+      if (!t.pdests && (g.in_place != 1 || y.k_out != y.k || y.v_out != y.v)) return KVC_E_ARG;
+      if ((z.flags & ~kScaleFlags) || z.reserved != 0 ||
+          ((z.flags & KVC_SCALE_K_UNIFORM) && (z.flags & KVC_SCALE_K_NONE)) ||
+          ((z.flags & KVC_SCALE_V_UNIFORM) && (z.flags & KVC_SCALE_V_NONE)))
         return KVC_E_ARG;
+      rc = scale_sides_check(z, true, g.num_pages, p->heads, g.page_size);
+      if (rc != KVC_OK) return rc;
+    }
+  }
+  if (t.pdests) {
+    if (t.scales && !t.dscales) return KVC_E_ARG;
+    for (int l = 0; l < nl; ++l) {
+      const kvc_layer_t& y = layers[l];
+      if (y.n_out == 0) continue;
+      if (t.pages[l].in_place != 0) return KVC_E_ARG;
+      const kvc_page_dest_t& d = t.pdests[l];
+      rc = page_dest_layer_check(p, y, d);
+      if (rc != KVC_OK) return rc;
+      if (!t.scales) continue;
+      const kvc_scales_t& dz = t.dscales[l];
+      if ((dz.flags & ~kScaleFlags) || dz.reserved != 0 || dz.flags != t.scales[l].flags)
+        return KVC_E_ARG;
+      rc = scale_sides_check(dz, false, d.num_pages, p->heads, d.page_size);
+      if (rc != KVC_OK) return rc;
     }
   }
   return KVC_OK;
 }
-
-// The destination side of a repage launch (kvc_launch_repage), handed to launch_chunk /
-// launch_chunk_ragged: their GATHER then is launch_gather_repage's.
-struct RepageArgs {
-  const kvc_page_dest_t* pdests;
-  const kvc_scales_t* dscales;  // with scales only
-};
 
 // Every launch goes through hipLaunchKernel, whose return value is this launch's own status (a
 // caller's pending HIP error is neither consumed nor reported as ours).
@@ -678,7 +649,7 @@ static int launch_gather_paged(const PagesChunk& C, int nl, int H, int BH, const
 
 // GATHER of a repage chunk (kvc_repage.h): grid (rows, passes of the chunk's longest output --
 // a ragged layer's envelope), the chunk's tables by value; the scale-carrying instances (fp8 rows,
-// cn <= kRepageScLayers) when scales move.  `ragged`: the chunk's entries, or nullptr.
+// cn <= kRepageScLayers) when scales move.  The chunk is layers c0 .. c0 + cn of the tables.
 template <typename C>
 static void fill_repage_tables(C* c, const kvc_layer_t* layers, const kvc_pages_t* pages,
                                const kvc_page_dest_t* pdests, int cn) {
@@ -688,11 +659,15 @@ static void fill_repage_tables(C* c, const kvc_layer_t* layers, const kvc_pages_
   memcpy(c->d, pdests, (size_t)cn * sizeof(kvc_page_dest_t));
 }
 template <int DT, int NC>
-static int launch_gather_repage(const kvc_layer_t* layers, const kvc_pages_t* pages,
-                                const kvc_ragged_t* ragged, const kvc_scales_t* scales,
-                                const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int cn,
+static int launch_gather_repage(const kvc_layer_t* all_layers, const Tables& t, int c0, int cn,
                                 int H, int BH, const int32_t* idx, int64_t istride, int shared,
                                 uint32_t* status, hipStream_t s) {
+  const kvc_layer_t* layers = all_layers + c0;
+  const kvc_pages_t* pages = t.pages + c0;
+  const kvc_page_dest_t* pdests = t.pdests + c0;
+  const kvc_ragged_t* ragged = t.ragged ? t.ragged + c0 : nullptr;
+  const kvc_scales_t* scales = t.scales ? t.scales + c0 : nullptr;
+  const kvc_scales_t* dscales = t.scales ? t.dscales + c0 : nullptr;
   const dim3 grid = pass_grid<NC>(layers, cn, BH, [](int) { return 0; });
   if (scales) {
     if constexpr (is_fp8(DT)) {
@@ -713,7 +688,7 @@ static int launch_gather_repage(const kvc_layer_t* layers, const kvc_pages_t* pa
       return launch_k(gather_repage_sc_kernel<DT, NC>, grid, dim3(kGatherThreads), 0, s, C, H, BH,
                       idx, istride, shared, status);
     } else {
-      return KVC_E_DTYPE;  // (plan_scaled_impl: scales belong to fp8 rows)
+      return KVC_E_DTYPE;  // (plan_tables: scales belong to fp8 rows)
     }
   }
   if (ragged) {
@@ -778,31 +753,85 @@ static int launch_select(const LayerChunk& T, int cn, int BH, int dt, int order,
   return go(std::false_type());
 }
 
+// What a chunk's launcher reads off the plan and the chunk's layers (c0 .. c0 + cn of nl) before
+// it launches anything: the workspace regions, the chunk's range of SCORE tiles, what its layers
+// ask of SELECT and GATHER, and the chunk's scale descriptions by value.
+struct ChunkPlan {
+  int H, BH;
+  char* norms;
+  int32_t* idx;
+  int64_t nstride, istride;     // of the norm / index rows
+  int64_t tile_base, tile_end;  // the chunk's SCORE tiles
+  int part;                     // KVC_FLAG_GATHER_FIXED / _SELECTED launches: the rows they copy
+  bool sel, snap, long_zone;    // some layer keeps selected rows / scores snapkv / needs scratch
+  int64_t max_out, max_part;    // longest output; longest output of this launch's `part`
+  uint32_t* status;
+  uint32_t* tmax;   // snapkv rows: SCORE's per-tile norm maxima (plan_impl reserved them)
+  ScalesChunk ZC;   // filled for scaled launches only (fp8: plan_tables)
+};
+static ChunkPlan chunk_plan(const kvc_params_t* p, const kvc_plan_info_t& info,
+                            const kvc_layer_t* layers, const Tables& t, int nl, int c0, int cn,
+                            char* w) {
+  ChunkPlan c;
+  c.H = p->heads, c.BH = p->batch * p->heads;
+  c.norms = w + info.norm_offset;
+  c.idx = reinterpret_cast<int32_t*>(w + info.index_offset);
+  c.nstride = info.norm_row_stride, c.istride = info.index_row_stride;
+  c.tile_base = layers[c0].tile0;
+  c.tile_end = c0 + cn < nl ? (int64_t)layers[c0 + cn].tile0 : info.score_tiles;
+  c.part = (p->flags & KVC_FLAG_GATHER_FIXED)      ? PART_FIXED
+           : (p->flags & KVC_FLAG_GATHER_SELECTED) ? PART_SELECTED
+                                                   : PART_ALL;
+  c.sel = c.long_zone = c.snap = false;
+  c.max_out = c.max_part = 0;
+  for (int l = c0; l < c0 + cn; ++l) {
+    c.sel |= layers[l].n_select > 0;
+    c.snap |= layer_selects(layers[l]) && layers[l].score_mode == KVC_SCORE_SNAPKV;
+    c.long_zone |= layer_selects(layers[l]) && layers[l].zone_len > kZoneMax;
+    c.max_out = layers[l].n_out > c.max_out ? layers[l].n_out : c.max_out;
+    const int64_t pr = part_rows(layers[l], c.part);
+    c.max_part = pr > c.max_part ? pr : c.max_part;
+  }
+  c.status = p->device_status;
+  c.tmax = c.snap && !p->external_index
+               ? reinterpret_cast<uint32_t*>(w + tmax_offset(info, p->dtype))
+               : nullptr;
+  if (t.scales) {
+    memset(&c.ZC, 0, sizeof(c.ZC));
+    memcpy(c.ZC.s, t.scales + c0, (size_t)cn * sizeof(kvc_scales_t));
+  }
+  return c;
+}
+
 // One chunk of <= kArgLayers layers: SCORE, then SELECT_GATHER (or SELECT and GATHER as two
 // kernels with KVC_FLAG_SPLIT_SELECT_GATHER, or GATHER alone for copy-only / external-index
 // calls), each kernel with the chunk's table by value.
-// dests != nullptr (kvc_launch_dest): SELECT and GATHER always as two kernels, the GATHER into the
-// layers' destinations (gather_dest_kernel).
-// pages != nullptr (kvc_launch_paged; cn <= kPagedLayers): SCORE and GATHER read K / V through the
-// layers' block tables (kvc_paged.h), SELECT as with dests.
-// scales != nullptr (kvc_launch_scaled; fp8, paged, in place): SCORE and GATHER are the scaled
-// instances, which also read / move the layers' scale words.
-// rp != nullptr (kvc_launch_repage; paged, out of place): SCORE and SELECT as above, GATHER through
-// the layers' destination tables (launch_gather_repage).
+// t.dests (kvc_launch_dest): SELECT and GATHER always as two kernels, the GATHER into the layers'
+// destinations (gather_dest_kernel).
+// t.pages (kvc_launch_paged; cn <= kPagedLayers): SCORE and GATHER read K / V through the layers'
+// block tables (kvc_paged.h), SELECT as with dests.
+// t.scales (kvc_launch_scaled; fp8, paged): SCORE and GATHER are the scaled instances, which also
+// read / move the layers' scale words.
+// t.pdests (kvc_launch_repage; paged, out of place): SCORE and SELECT as above, GATHER through the
+// layers' destination tables (launch_gather_repage).
 template <int DT, int NC>
 static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, const kvc_layer_t* layers,
-                        int nl, int c0, int cn, char* w, hipStream_t s,
-                        const kvc_dest_t* dests = nullptr,
-                        const kvc_pages_t* pages = nullptr,
-                        const kvc_scales_t* scales = nullptr, const RepageArgs* rp = nullptr) {
+                        const Tables& t, int nl, int c0, int cn, char* w, hipStream_t s) {
   typedef typename DTypeTraits<DT>::key_t KeyT;
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;  // selection binary: the key class
   constexpr int SDT = score_dt(DT);  // the selection's runtime dtype (bf16 for fp8 rows)
   constexpr bool F8 = is_fp8(DT);    // the fused kernel's row copy: bytes, no NaN rewrite
-  const int H = p->heads, BH = p->batch * p->heads;
-  char* norms = w + info.norm_offset;
-  int32_t* idx = reinterpret_cast<int32_t*>(w + info.index_offset);
-  const int64_t nstride = info.norm_row_stride, istride = info.index_row_stride;
+  const ChunkPlan c = chunk_plan(p, info, layers, t, nl, c0, cn, w);
+  const int H = c.H, BH = c.BH, part = c.part;
+  char* const norms = c.norms;
+  int32_t* const idx = c.idx;
+  const int64_t nstride = c.nstride, istride = c.istride;
+  const int64_t tile_base = c.tile_base, tile_end = c.tile_end;
+  uint32_t* const status = c.status;
+  uint32_t* const tmax = c.tmax;
+  const kvc_dest_t* dests = t.dests;
+  const kvc_pages_t* pages = t.pages;
+  const kvc_scales_t* scales = t.scales;
 #ifdef KVC_STAMPS
   uint64_t* stamps = reinterpret_cast<uint64_t*>(w + info.workspace_bytes - info.rows * 256);
 #else
@@ -810,34 +839,11 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
 #endif
   LayerChunk T;
   memcpy(T.l, layers + c0, (size_t)cn * sizeof(kvc_layer_t));
-  const int64_t tile_base = layers[c0].tile0;
-  const int64_t tile_end = c0 + cn < nl ? (int64_t)layers[c0 + cn].tile0 : info.score_tiles;
-  const int part = (p->flags & KVC_FLAG_GATHER_FIXED)      ? PART_FIXED
-                   : (p->flags & KVC_FLAG_GATHER_SELECTED) ? PART_SELECTED
-                                                           : PART_ALL;
-  bool sel = false, long_zone = false, snap = false;
-  int64_t max_out = 0, max_part = 0;
-  for (int l = c0; l < c0 + cn; ++l) {
-    sel |= layers[l].n_select > 0;
-    snap |= layer_selects(layers[l]) && layers[l].score_mode == KVC_SCORE_SNAPKV;
-    long_zone |= layer_selects(layers[l]) && layers[l].zone_len > kZoneMax;
-    max_out = layers[l].n_out > max_out ? layers[l].n_out : max_out;
-    const int64_t pr = part_rows(layers[l], part);
-    max_part = pr > max_part ? pr : max_part;
-  }
   const bool ext = p->external_index != 0;
-  uint32_t* status = p->device_status;
-  // snapkv rows: SCORE's per-tile norm maxima (plan_impl reserved them), read by the selection
-  uint32_t* tmax = snap && !ext ? reinterpret_cast<uint32_t*>(w + tmax_offset(info, p->dtype))
-                                : nullptr;
   int rc = KVC_OK;
   PagesChunk PC;  // filled for paged launches only
   if (pages) fill_pages_chunk(&PC, p, layers + c0, pages + c0, dests ? dests + c0 : nullptr, cn);
-  ScalesChunk ZC;  // filled for scaled launches only
-  if (scales) {
-    memset(&ZC, 0, sizeof(ZC));
-    memcpy(ZC.s, scales + c0, (size_t)cn * sizeof(kvc_scales_t));
-  }
+  const ScalesChunk& ZC = c.ZC;
   if constexpr (is_fp8(DT)) {
     if (scales && (p->phases & KVC_PHASE_SCORE) && tile_end > tile_base && !ext) {
       constexpr int per_wg = score_waves(NC);
@@ -855,9 +861,9 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
                                       tmax, s);
   if (rc != KVC_OK) return rc;
   const int n_cap = (int)nstride;  // longest zone of the call, rounded to 64
-  if ((p->phases & KVC_PHASE_SELECT) && sel && !ext) {
-    const bool fuse_sg = (p->phases & KVC_PHASE_GATHER) && max_out > 0 && !stamps &&
-                         !long_zone && part == PART_ALL && !dests && !pages &&
+  if ((p->phases & KVC_PHASE_SELECT) && c.sel && !ext) {
+    const bool fuse_sg = (p->phases & KVC_PHASE_GATHER) && c.max_out > 0 && !stamps &&
+                         !c.long_zone && part == PART_ALL && !dests && !pages &&
                          !(p->flags & KVC_FLAG_SPLIT_SELECT_GATHER);
     if (fuse_sg) {  // this chunk's gather happens inside the select kernel
       const int rows = cn * BH;
@@ -901,34 +907,23 @@ static int launch_chunk(const kvc_params_t* p, const kvc_plan_info_t& info, cons
     char* scratch = w + round_up(info.index_offset + (size_t)info.rows * istride * 4, 256);
     uint64_t* st = stamps ? stamps + (size_t)layers[c0].row0 * 32 : nullptr;
     rc = launch_select<KC>(T, cn, BH, SDT, p->order, p->algo, norms, nstride, idx, istride,
-                           long_zone, scratch, st, status, s, tmax);
+                           c.long_zone, scratch, st, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
-  if (rp) {
-    if (!((p->phases & KVC_PHASE_GATHER) && max_part > 0)) return rc;
-    return launch_gather_repage<DT, NC>(layers + c0, pages + c0, nullptr,
-                                        scales ? scales + c0 : nullptr, rp->pdests + c0,
-                                        scales ? rp->dscales + c0 : nullptr, cn, H, BH, idx,
-                                        istride, (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0,
-                                        status, s);
-  }
+  if (!((p->phases & KVC_PHASE_GATHER) && c.max_part > 0)) return rc;  // no GATHER to run
+  const int shared = (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0;
+  if (t.pdests)
+    return launch_gather_repage<DT, NC>(layers, t, c0, cn, H, BH, idx, istride, shared, status, s);
   if constexpr (is_fp8(DT)) {
-    if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && scales)  // every layer in place
+    if (scales)  // every layer in place
       return launch_k(gather_paged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
                       dim3(kGatherThreads), 0, s, PC, ZC, H, BH, static_cast<const int32_t*>(idx),
-                      istride, (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status);
+                      istride, shared, status);
   }
-  if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && pages)
-    return launch_gather_paged<DT, NC>(PC, cn, H, BH, idx, istride,
-                                       (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
-  if ((p->phases & KVC_PHASE_GATHER) && max_part > 0 && dests)
-    return launch_gather_dest<DT, NC>(T, dests + c0, cn, H, BH, idx, istride,
-                                      (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, s);
-  if ((p->phases & KVC_PHASE_GATHER) && max_part > 0)
-    rc = launch_gather<DT, NC>(T, cn, H, BH, idx, istride,
-                               (p->flags & KVC_FLAG_SHARED_INDEX) ? 1 : 0, status, max_part, part,
-                               s);
-  return rc;
+  if (pages) return launch_gather_paged<DT, NC>(PC, cn, H, BH, idx, istride, shared, status, s);
+  if (dests)
+    return launch_gather_dest<DT, NC>(T, dests + c0, cn, H, BH, idx, istride, shared, status, s);
+  return launch_gather<DT, NC>(T, cn, H, BH, idx, istride, shared, status, c.max_part, part, s);
 }
 
 // SELECT of a ragged chunk: launch_select's choice of kernel class by the call's longest
@@ -972,43 +967,29 @@ static int launch_select_ragged(const RaggedChunk& C, int cn, int H, int BH, int
 }
 
 // One chunk of <= kPagedLayers ragged layers: SCORE, SELECT and GATHER as three kernels, grids and
-// kernel classes by the layers' envelopes (what plan_ragged_impl left in the table), each row's
-// bounds from its device record.
+// kernel classes by the layers' envelopes (what plan_tables' ragged step left in the table), each
+// row's bounds from its device record.  (A ragged call has no external index and copies every
+// part: ChunkPlan's tmax and max_part are the plain ones.)
 template <int DT, int NC>
 static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& info,
-                               const kvc_layer_t* layers, const kvc_pages_t* pages,
-                               const kvc_ragged_t* ragged, int nl, int c0, int cn, char* w,
-                               hipStream_t s, const kvc_scales_t* scales = nullptr,
-                               const RepageArgs* rp = nullptr) {
+                               const kvc_layer_t* layers, const Tables& t, int nl, int c0, int cn,
+                               char* w, hipStream_t s) {
   constexpr int KC = DT == KVC_F32 ? KVC_F32 : KVC_BF16;
-  const int H = p->heads, BH = p->batch * p->heads;
-  char* norms = w + info.norm_offset;
-  int32_t* idx = reinterpret_cast<int32_t*>(w + info.index_offset);
-  const int64_t nstride = info.norm_row_stride, istride = info.index_row_stride;
+  const ChunkPlan c = chunk_plan(p, info, layers, t, nl, c0, cn, w);
+  const int H = c.H, BH = c.BH;
+  char* const norms = c.norms;
+  int32_t* const idx = c.idx;
+  const int64_t nstride = c.nstride, istride = c.istride;
+  uint32_t* const status = c.status;
+  uint32_t* const tmax = c.tmax;
+  const ScalesChunk& ZC = c.ZC;
   RaggedChunk C;
   memset(&C, 0, sizeof(C));
   memcpy(C.l, layers + c0, (size_t)cn * sizeof(kvc_layer_t));
-  memcpy(C.p, pages + c0, (size_t)cn * sizeof(kvc_pages_t));
-  for (int l = 0; l < cn; ++l) C.s[l] = ragged[c0 + l].dev;
-  ScalesChunk ZC;  // filled for scaled launches only (fp8: plan_scaled_impl)
-  if (scales) {
-    memset(&ZC, 0, sizeof(ZC));
-    memcpy(ZC.s, scales + c0, (size_t)cn * sizeof(kvc_scales_t));
-  }
-  const int64_t tile_base = layers[c0].tile0;
-  const int64_t tile_end = c0 + cn < nl ? (int64_t)layers[c0 + cn].tile0 : info.score_tiles;
-  bool sel = false, long_zone = false, snap = false;
-  int64_t max_out = 0;
-  for (int l = c0; l < c0 + cn; ++l) {
-    sel |= layers[l].n_select > 0;
-    snap |= layer_selects(layers[l]) && layers[l].score_mode == KVC_SCORE_SNAPKV;
-    long_zone |= layer_selects(layers[l]) && layers[l].zone_len > kZoneMax;
-    max_out = layers[l].n_out > max_out ? layers[l].n_out : max_out;
-  }
-  uint32_t* status = p->device_status;
-  uint32_t* tmax = snap ? reinterpret_cast<uint32_t*>(w + tmax_offset(info, p->dtype)) : nullptr;
+  memcpy(C.p, t.pages + c0, (size_t)cn * sizeof(kvc_pages_t));
+  for (int l = 0; l < cn; ++l) C.s[l] = t.ragged[c0 + l].dev;
   int rc = KVC_OK;
-  if ((p->phases & KVC_PHASE_SCORE) && tile_end > tile_base) {  // some envelope selects
+  if ((p->phases & KVC_PHASE_SCORE) && c.tile_end > c.tile_base) {  // some envelope selects
     int64_t zmax = 0;  // the chunk's longest selecting envelope zone
     for (int l = c0; l < c0 + cn; ++l)
       if (layer_selects(layers[l]) && layers[l].zone_len > zmax) zmax = layers[l].zone_len;
@@ -1016,7 +997,7 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
     const dim3 grid((unsigned)(cn * BH), (unsigned)((zmax + per_block - 1) / per_block));
     bool done = false;
     if constexpr (is_fp8(DT)) {
-      if (scales) {
+      if (t.scales) {
         rc = launch_k(score_ragged_scaled_kernel<DT, NC>, grid, dim3(score_waves(NC) * 64), 0, s,
                       C, ZC, H, BH, norms, nstride, tmax, nstride / kTile, status);
         done = true;
@@ -1027,28 +1008,50 @@ static int launch_chunk_ragged(const kvc_params_t* p, const kvc_plan_info_t& inf
                     norms, nstride, tmax, nstride / kTile, status);
   }
   if (rc != KVC_OK) return rc;
-  if ((p->phases & KVC_PHASE_SELECT) && sel) {
+  if ((p->phases & KVC_PHASE_SELECT) && c.sel) {
     char* scratch = w + round_up(info.index_offset + (size_t)info.rows * istride * 4, 256);
     rc = launch_select_ragged<KC>(C, cn, H, BH, score_dt(DT), p->order, p->algo, norms, nstride, idx,
-                                  istride, long_zone, scratch, status, s, tmax);
+                                  istride, c.long_zone, scratch, status, s, tmax);
   }
   if (rc != KVC_OK) return rc;
-  if (rp) {  // kvc_launch_repage: out of place, through the destination tables
-    if (!((p->phases & KVC_PHASE_GATHER) && max_out > 0)) return rc;
-    return launch_gather_repage<DT, NC>(layers + c0, pages + c0, ragged + c0,
-                                        scales ? scales + c0 : nullptr, rp->pdests + c0,
-                                        scales ? rp->dscales + c0 : nullptr, cn, H, BH, idx,
-                                        istride, 0, status, s);
-  }
+  if (!((p->phases & KVC_PHASE_GATHER) && c.max_out > 0)) return rc;  // no GATHER to run
+  if (t.pdests)  // out of place, through the destination tables (every row has its own indices)
+    return launch_gather_repage<DT, NC>(layers, t, c0, cn, H, BH, idx, istride, 0, status, s);
   if constexpr (is_fp8(DT)) {
-    if ((p->phases & KVC_PHASE_GATHER) && max_out > 0 && scales)
+    if (t.scales)
       return launch_k(gather_ragged_scaled_kernel<DT, NC>, dim3((unsigned)(cn * BH)),
                       dim3(kGatherThreads), 0, s, C, ZC, H, BH, static_cast<const int32_t*>(idx),
                       istride, status);
   }
-  if ((p->phases & KVC_PHASE_GATHER) && max_out > 0)
-    rc = launch_k(gather_ragged_kernel<DT, NC>, dim3((unsigned)(cn * BH)), dim3(kGatherThreads), 0,
+  return launch_k(gather_ragged_kernel<DT, NC>, dim3((unsigned)(cn * BH)), dim3(kGatherThreads), 0,
                   s, C, H, BH, static_cast<const int32_t*>(idx), istride, status);
+}
+
+// The launch of every entry point: the plan again (comparing, not filling), then the layers in
+// argument chunks, each through the launcher of its dtype and row width.
+static int launch_tables(const kvc_params_t* p, const kvc_layer_t* layers, const Tables& t, int nl,
+                         void* ws, size_t ws_bytes, kvc_stream_t stream) {
+  kvc_plan_info_t info;
+  int rc = plan_tables(p, const_cast<kvc_layer_t*>(layers), t, nl, &info, false);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0) return KVC_OK;
+  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  const int nc = p->head_dim * esize(p->dtype) / 16;
+  // layers per argument chunk: paged chunks carry more tables per layer, and the scale-carrying
+  // copy through destination tables two scale descriptions as well
+  const int step = !t.pages ? kArgLayers : (t.pdests && t.scales) ? kRepageScLayers : kPagedLayers;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
+    const int cn = nl - c0 < step ? nl - c0 : step;
+    rc = with_kv_dtype(p->dtype, [&](auto dt) {
+      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
+        constexpr int DT = decltype(dt)::value, NC = decltype(ncv)::value;
+        if (t.ragged) return launch_chunk_ragged<DT, NC>(p, info, layers, t, nl, c0, cn, w, s);
+        return launch_chunk<DT, NC>(p, info, layers, t, nl, c0, cn, w, s);
+      });
+    });
+  }
   return rc;
 }
 
@@ -1260,161 +1263,78 @@ const char* kvc_status_string(int s) {
   }
 }
 
+// The plan / launch pairs: each names the tables it has (kvc::Tables' order: dests, pages,
+// ragged, scales, pdests, dscales) for kvc::plan_tables / kvc::launch_tables.
 int kvc_plan(const kvc_params_t* params, kvc_layer_t* layers, int num_layers,
              kvc_plan_info_t* info) {
-  return kvc::plan_impl(params, layers, num_layers, info, true);
-}
-
-int kvc_plan_dest(const kvc_params_t* params, kvc_layer_t* layers, const kvc_dest_t* dests,
-                  int num_layers, kvc_plan_info_t* info) {
-  return kvc::plan_dest_impl(params, layers, dests, num_layers, info, true);
+  return kvc::plan_tables(params, layers, {}, num_layers, info, true);
 }
 
 int kvc_launch(const kvc_params_t* p, const kvc_layer_t* layers, int nl, void* ws,
                size_t ws_bytes, kvc_stream_t stream) {
-  return kvc_launch_dest(p, layers, nullptr, nl, ws, ws_bytes, stream);
+  return kvc::launch_tables(p, layers, {}, nl, ws, ws_bytes, stream);
+}
+
+int kvc_plan_dest(const kvc_params_t* params, kvc_layer_t* layers, const kvc_dest_t* dests,
+                  int num_layers, kvc_plan_info_t* info) {
+  return kvc::plan_tables(params, layers, {dests}, num_layers, info, true);
 }
 
 int kvc_launch_dest(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_dest_t* dests,
                     int nl, void* ws, size_t ws_bytes, kvc_stream_t stream) {
-  return kvc_launch_paged(p, layers, nullptr, dests, nl, ws, ws_bytes, stream);
+  return kvc::launch_tables(p, layers, {dests}, nl, ws, ws_bytes, stream);
 }
 
 int kvc_plan_paged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
                    const kvc_dest_t* dests, int num_layers, kvc_plan_info_t* info) {
-  return kvc::plan_paged_impl(params, layers, pages, dests, num_layers, info, true);
+  return kvc::plan_tables(params, layers, {dests, pages}, num_layers, info, true);
 }
 
 int kvc_launch_paged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
                      const kvc_dest_t* dests, int nl, void* ws, size_t ws_bytes,
                      kvc_stream_t stream) {
-  using namespace kvc;
-  kvc_plan_info_t info;
-  int rc = plan_paged_impl(p, const_cast<kvc_layer_t*>(layers), pages, dests, nl, &info, false);
-  if (rc != KVC_OK) return rc;
-  if (nl == 0) return KVC_OK;
-  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  const int nc = p->head_dim * esize(p->dtype) / 16;
-  const int step = pages ? kPagedLayers : kArgLayers;  // layers per argument chunk
-  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
-    const int cn = nl - c0 < step ? nl - c0 : step;
-    rc = with_kv_dtype(p->dtype, [&](auto dt) {
-      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
-        return launch_chunk<decltype(dt)::value, decltype(ncv)::value>(p, info, layers, nl, c0,
-                                                                       cn, w, s, dests, pages);
-      });
-    });
-  }
-  return rc;
+  return kvc::launch_tables(p, layers, {dests, pages}, nl, ws, ws_bytes, stream);
 }
 
 int kvc_plan_ragged(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
                     const kvc_ragged_t* ragged, int num_layers, kvc_plan_info_t* info) {
-  return kvc::plan_ragged_impl(params, layers, pages, ragged, num_layers, info, true);
+  return kvc::plan_tables(params, layers, {nullptr, pages, ragged}, num_layers, info, true);
 }
 
 int kvc_launch_ragged(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
                       const kvc_ragged_t* ragged, int nl, void* ws, size_t ws_bytes,
                       kvc_stream_t stream) {
-  using namespace kvc;
-  if (!ragged) return kvc_launch_paged(p, layers, pages, nullptr, nl, ws, ws_bytes, stream);
-  kvc_plan_info_t info;
-  int rc = plan_ragged_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, nl, &info, false);
-  if (rc != KVC_OK) return rc;
-  if (nl == 0) return KVC_OK;
-  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  const int nc = p->head_dim * esize(p->dtype) / 16;
-  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kPagedLayers) {
-    const int cn = nl - c0 < kPagedLayers ? nl - c0 : kPagedLayers;
-    rc = with_kv_dtype(p->dtype, [&](auto dt) {
-      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
-        return launch_chunk_ragged<decltype(dt)::value, decltype(ncv)::value>(
-            p, info, layers, pages, ragged, nl, c0, cn, w, s);
-      });
-    });
-  }
-  return rc;
+  return kvc::launch_tables(p, layers, {nullptr, pages, ragged}, nl, ws, ws_bytes, stream);
 }
 
 int kvc_plan_scaled(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
                     const kvc_ragged_t* ragged, const kvc_scales_t* scales, int num_layers,
                     kvc_plan_info_t* info) {
-  return kvc::plan_scaled_impl(params, layers, pages, ragged, scales, num_layers, info, true);
+  return kvc::plan_tables(params, layers, {nullptr, pages, ragged, scales}, num_layers, info,
+                          true);
 }
 
 int kvc_launch_scaled(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
                       const kvc_ragged_t* ragged, const kvc_scales_t* scales, int nl, void* ws,
                       size_t ws_bytes, kvc_stream_t stream) {
-  using namespace kvc;
-  if (!scales) return kvc_launch_ragged(p, layers, pages, ragged, nl, ws, ws_bytes, stream);
-  kvc_plan_info_t info;
-  int rc = plan_scaled_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, scales, nl, &info,
-                            false);
-  if (rc != KVC_OK) return rc;
-  if (nl == 0) return KVC_OK;
-  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  const int nc = p->head_dim * esize(p->dtype) / 16;
-  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kPagedLayers) {
-    const int cn = nl - c0 < kPagedLayers ? nl - c0 : kPagedLayers;
-    rc = with_kv_dtype(p->dtype, [&](auto dt) {
-      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
-        constexpr int DT = decltype(dt)::value, NC = decltype(ncv)::value;
-        if (ragged)
-          return launch_chunk_ragged<DT, NC>(p, info, layers, pages, ragged, nl, c0, cn, w, s,
-                                             scales);
-        return launch_chunk<DT, NC>(p, info, layers, nl, c0, cn, w, s, nullptr, pages, scales);
-      });
-    });
-  }
-  return rc;
+  return kvc::launch_tables(p, layers, {nullptr, pages, ragged, scales}, nl, ws, ws_bytes,
+                            stream);
 }
 
 int kvc_plan_repage(const kvc_params_t* params, kvc_layer_t* layers, const kvc_pages_t* pages,
                     const kvc_ragged_t* ragged, const kvc_scales_t* scales,
                     const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int num_layers,
                     kvc_plan_info_t* info) {
-  return kvc::plan_repage_impl(params, layers, pages, ragged, scales, pdests, dscales, num_layers,
-                               info, true);
+  return kvc::plan_tables(params, layers, {nullptr, pages, ragged, scales, pdests, dscales},
+                          num_layers, info, true);
 }
 
 int kvc_launch_repage(const kvc_params_t* p, const kvc_layer_t* layers, const kvc_pages_t* pages,
                       const kvc_ragged_t* ragged, const kvc_scales_t* scales,
                       const kvc_page_dest_t* pdests, const kvc_scales_t* dscales, int nl, void* ws,
                       size_t ws_bytes, kvc_stream_t stream) {
-  using namespace kvc;
-  if (!pdests) return kvc_launch_scaled(p, layers, pages, ragged, scales, nl, ws, ws_bytes, stream);
-  kvc_plan_info_t info;
-  int rc = plan_repage_impl(p, const_cast<kvc_layer_t*>(layers), pages, ragged, scales, pdests,
-                            dscales, nl, &info, false);
-  if (rc != KVC_OK) return rc;
-  if (nl == 0) return KVC_OK;
-  if (!ws || ws_bytes < info.workspace_bytes) return KVC_E_WORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  const int nc = p->head_dim * esize(p->dtype) / 16;
-  const RepageArgs rp = {pdests, dscales};
-  // layers per argument chunk: the scale-carrying copy takes two scale descriptions per layer
-  const int step = scales ? kRepageScLayers : kPagedLayers;
-  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += step) {
-    const int cn = nl - c0 < step ? nl - c0 : step;
-    rc = with_kv_dtype(p->dtype, [&](auto dt) {
-      return with_nc_dt<decltype(dt)::value>(nc, [&](auto ncv) {
-        constexpr int DT = decltype(dt)::value, NC = decltype(ncv)::value;
-        if (ragged)
-          return launch_chunk_ragged<DT, NC>(p, info, layers, pages, ragged, nl, c0, cn, w, s,
-                                             scales, &rp);
-        return launch_chunk<DT, NC>(p, info, layers, nl, c0, cn, w, s, nullptr, pages, scales,
-                                    &rp);
-      });
-    });
-  }
-  return rc;
+  return kvc::launch_tables(p, layers, {nullptr, pages, ragged, scales, pdests, dscales}, nl, ws,
+                            ws_bytes, stream);
 }
 
 int kvc_compress(const kvc_params_t* params, kvc_layer_t* layers, int num_layers, void* ws,

@@ -6,6 +6,7 @@ arithmetic) and, for every layer that the reference would gather/concatenate, re
 batched engine launch per (device, dtype, batch, heads, head_dim) group -- score, select and
 gather kernels over every layer at once -- and writes the new (K, V) tensors back into the list.
 """
+import contextlib
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -309,28 +310,16 @@ def _one_plain_group(jobs):
     return dev, dt, B, H, D, kps, vps, segs
 
 
-def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None, scales=None,
-            pdests=None, dscales=None):
-    """Plan one table and allocate its workspace.  The table itself travels in the kernels'
-    arguments; caller-provided indices (strategy="random") are copied into the index region here."""
-    if pdests is not None:  # paged layers delivered through a second block table
-        rc, info = N.plan_repage(params, table, pages, ragged, scales, pdests, dscales)
-        N.check(rc, "kvc_plan_repage")
-    elif scales is not None:  # scaled fp8 paged layers, compacted in place (ragged or not)
-        rc, info = N.plan_scaled(params, table, pages, ragged, scales)
-        N.check(rc, "kvc_plan_scaled")
-    elif ragged is not None:
-        rc, info = N.plan_ragged(params, table, pages, ragged)
-        N.check(rc, "kvc_plan_ragged")
-    elif pages is not None:
-        rc, info = N.plan_paged(params, table, pages, dests)
-        N.check(rc, "kvc_plan_paged")
-    elif dests is None:
+def _upload(params, table, device, js, B, H, tables=None):
+    """Plan one table -- with the call's optional tables, an N.Tables; a dense call has none --
+    and allocate its workspace.  The table itself travels in the kernels' arguments;
+    caller-provided indices (strategy="random") are copied into the index region here."""
+    if tables is None:
         rc, info = N.plan(params, table)
         N.check(rc, "kvc_plan")
     else:
-        rc, info = N.plan_dest(params, table, dests)
-        N.check(rc, "kvc_plan_dest")
+        rc, info = tables.plan(params, table)
+        N.check(rc, tables.plan_name)
     ws = torch.empty(max(int(info.workspace_bytes), 256), dtype=torch.uint8, device=device)
     if params.external_index:
         istride = int(info.index_row_stride)
@@ -343,9 +332,11 @@ def _upload(params, table, device, js, B, H, dests=None, pages=None, ragged=None
     return ws, info
 
 
-def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, ragged=None,
-            scales=None, pdests=None, dscales=None):
+def _launch(params, table, ws, info, stream, phases, tables=None):
     _touch(ws.get_device())  # a cached plan's Params makes no status_word() call
+    # the entry point of the call's tables, resolved once for all of its timed phases
+    launch, what = (N.launch, "kvc_launch") if tables is None else \
+        (tables.launch, tables.launch_name)
     saved = params.phases
     steps = _timer.steps if _timer is not None and _timer.split else (("all", phases),)
     for name, bits in steps:
@@ -355,31 +346,10 @@ def _launch(params, table, ws, info, stream, phases, dests=None, pages=None, rag
         if _timer is not None:
             a, b = _timer.event(), _timer.event()
             a.record(stream)
-        if pdests is not None:
-            rc = N.launch_repage(params, table, pages, ragged, scales, pdests, dscales,
-                                 ws.data_ptr(), int(info.workspace_bytes), stream.cuda_stream)
-        elif scales is not None:
-            rc = N.launch_scaled(params, table, pages, ragged, scales, ws.data_ptr(),
-                                 int(info.workspace_bytes), stream.cuda_stream)
-        elif ragged is not None:
-            rc = N.launch_ragged(params, table, pages, ragged, ws.data_ptr(),
-                                 int(info.workspace_bytes), stream.cuda_stream)
-        elif pages is not None:
-            rc = N.launch_paged(params, table, pages, dests, ws.data_ptr(),
-                                int(info.workspace_bytes), stream.cuda_stream)
-        elif dests is None:
-            rc = N.launch(params, table, ws.data_ptr(), int(info.workspace_bytes),
-                          stream.cuda_stream)
-        else:
-            rc = N.launch_dest(params, table, dests, ws.data_ptr(), int(info.workspace_bytes),
-                               stream.cuda_stream)
+        rc = launch(params, table, ws.data_ptr(), int(info.workspace_bytes), stream.cuda_stream)
         if _timer is not None:
             b.record(stream)
-        N.check(rc, "kvc_launch_repage" if pdests is not None else
-                "kvc_launch_scaled" if scales is not None else
-                "kvc_launch_ragged" if ragged is not None else
-                "kvc_launch_paged" if pages is not None else
-                "kvc_launch" if dests is None else "kvc_launch_dest")
+        N.check(rc, what)
         if _timer is not None:
             _timer.records.append((name, a, b))
     params.phases = saved
@@ -789,7 +759,7 @@ def execute_shared(jobs: List[Segments], out_list: list, fill, overlap=False):
                     _launch(pf, table, ws, info, side[0], pf.phases)
                 fill(js, ws.data_ptr() + int(info.index_offset), int(info.index_row_stride),
                      stream)
-                _launch(p, table, ws, info, stream, p.phases, dests)
+                _launch(p, table, ws, info, stream, p.phases, N.Tables(dests) if dest else None)
             finally:
                 if side is not None:  # `stream` continues only after the side copy, on every
                     side[2].record(side[0])  # exit path (outputs and workspace are freed on it)
@@ -986,7 +956,7 @@ def _run_dest(jobs, out_list, order, algo):
             stream = torch.cuda.current_stream(device)
             p = _params(dtype, B, H, D, order, algo, external)  # first: see execute_shared
             table, kos, vos, keep = _build_table(device, dtype, B, H, D, js, True)
-            dests = _dest_table(js, table)
+            dests = N.Tables(_dest_table(js, table))
             ws, info = _upload(p, table, device, js, B, H, dests)
             _launch(p, table, ws, info, stream, p.phases, dests)
             if _timer is not None and _timer.workspaces is not None:
@@ -1238,17 +1208,8 @@ def dest_call(fn, past_key_values, out, args, kwargs):
                     raise ValueError(f"layer {i}: {name} shares its memory with {seen[ptr]}: "
                                      "not compacted in place")
                 seen[ptr] = f"layer {i}'s {name}"
-    ctx = _DestCall(dests)
-    prev = getattr(_dest_state, "ctx", None)
-    try:
-        _dest_state.ctx = ctx
-        try:
-            res = fn(kvl, *args, **kwargs)  # launches nothing on K / V: see _defer()
-        finally:
-            _dest_state.ctx = prev
-        if not isinstance(res, list):
-            res = list(res)
-        moves = _dest_moves(kvl, res, dests, ctx)
+    res, moves, ctx = _deferred(fn, kvl, dests, args, kwargs)
+    with _rolled_back(ctx):
         # every job of the call -- the method's and the copies -- is checked before any launches
         every = [j for jobs, _, _ in ctx.pending for j in jobs] + moves
         for j in every:
@@ -1257,10 +1218,6 @@ def dest_call(fn, past_key_values, out, args, kwargs):
                 j.dest_verified = True
         for j in every:
             _check_tensors(j)
-    except BaseException:
-        for undo in reversed(ctx.rollback):
-            undo()
-        raise
     for jobs, run, out_list in ctx.pending:
         run()
         if out_list is not res:
@@ -1268,6 +1225,37 @@ def dest_call(fn, past_key_values, out, args, kwargs):
                 res[j.layer_idx] = out_list[j.layer_idx]
     execute(moves, res, N.KVC_ASC, N.KVC_ALGO_SORT)
     return res
+
+
+@contextlib.contextmanager
+def _rolled_back(ctx):
+    """The reach of a deferred call's rollback: an exception raised inside runs ctx.rollback,
+    newest first, and goes on.  For the checks a caller of _deferred makes before it launches."""
+    try:
+        yield
+    except BaseException:
+        for undo in reversed(ctx.rollback):
+            undo()
+        raise
+
+
+def _deferred(fn, kvl, dests, args=(), kwargs=None):
+    """The deferred call of `fn` on the (K, V) list `kvl` with destinations `dests`: a fresh
+    _DestCall installed while fn's own Python runs -- which launches nothing on K / V, see
+    _defer() -- the previous context restored, then the copy-only jobs of the layers that no
+    engine job delivered.  Returns (fn's result as a list, those moves, the _DestCall with the
+    parked launches); an exception on the way is rolled back (_rolled_back)."""
+    ctx = _DestCall(dests)
+    prev = getattr(_dest_state, "ctx", None)
+    with _rolled_back(ctx):
+        _dest_state.ctx = ctx
+        try:
+            res = fn(kvl, *args, **(kwargs or {}))
+        finally:
+            _dest_state.ctx = prev
+        if not isinstance(res, list):
+            res = list(res)
+        return res, _dest_moves(kvl, res, dests, ctx), ctx
 
 
 def _dest_moves(kvl, res, dests, ctx):

@@ -382,6 +382,48 @@ def launch_repage(params, table, pages, ragged, scales, pdests, dscales, ws_ptr,
                                    _opt(dscales, SCALES_DTYPE, n), n, ws_ptr, ws_bytes, stream_ptr)
 
 
+class Tables:
+    """The optional tables of one call (csrc/kvc.hip, struct Tables): per field an array of one
+    record per layer, or None for a call without that table.  The one place that knows which
+    plan / launch pair serves which combination, and under what name its errors are reported
+    (`plan_name` / `launch_name`, for check())."""
+    __slots__ = ("dests", "pages", "ragged", "scales", "pdests", "dscales", "_entry", "_args")
+
+    def __init__(self, dests=None, pages=None, ragged=None, scales=None, pdests=None,
+                 dscales=None):
+        self.dests, self.pages, self.ragged = dests, pages, ragged
+        self.scales, self.pdests, self.dscales = scales, pdests, dscales
+        if pdests is not None:  # paged layers delivered through a second block table
+            self._entry, self._args = "_repage", (pages, ragged, scales, pdests, dscales)
+        elif scales is not None:  # scaled fp8 paged layers, compacted in place (ragged or not)
+            self._entry, self._args = "_scaled", (pages, ragged, scales)
+        elif ragged is not None:
+            self._entry, self._args = "_ragged", (pages, ragged)
+        elif pages is not None:
+            self._entry, self._args = "_paged", (pages, dests)
+        elif dests is not None:
+            self._entry, self._args = "_dest", (dests,)
+        else:
+            self._entry, self._args = "", ()
+
+    @property
+    def plan_name(self):
+        return "kvc_plan" + self._entry
+
+    @property
+    def launch_name(self):
+        return "kvc_launch" + self._entry
+
+    def plan(self, params, table):
+        """(rc, PlanInfo) of the combination's kvc_plan* entry (this module's plan* function)."""
+        return globals()["plan" + self._entry](params, table, *self._args)
+
+    def launch(self, params, table, ws_ptr, ws_bytes, stream_ptr):
+        """rc of the combination's kvc_launch* entry (this module's launch* function)."""
+        return globals()["launch" + self._entry](params, table, *self._args, ws_ptr, ws_bytes,
+                                                 stream_ptr)
+
+
 def attn_accumulate(params, table, stream_ptr):
     return lib().kvc_attn_accumulate(ctypes.byref(params), table.ctypes.data, len(table),
                                      stream_ptr)

@@ -23,6 +23,50 @@ from . import _engine as E
 from . import _native as N
 
 
+def _check_pool_view(what, t, device=None):
+    """A K / V pool view [num_pages, H, page_size, D] that the kernels can address as it is (a
+    pool is never copied): a page size that is a power of two, a contiguous last dim, rows and
+    strides of multiples of 16 bytes, no stride 0 over a dim larger than 1, a 16-byte aligned
+    pointer -- and, given `device`, on that device.  `what` names the pool: "PagedKV: k_pool"."""
+    npg, H, P, D = t.shape
+    es = t.element_size()
+    if npg < 1 or H < 1 or D < 1 or P < 1 or P > 65536 or P & (P - 1):
+        raise ValueError(f"{what}: page_size must be a power of two in [1, 65536] and the pool "
+                         f"non-empty; got a pool of shape {tuple(t.shape)}")
+    if (t.stride(3) != 1 and D > 1) or (D * es) % 16 or any(
+            (t.stride(d) * es) % 16 and t.size(d) > 1 for d in range(3)):
+        raise ValueError(f"{what} needs a contiguous last dim and rows and strides that are "
+                         f"multiples of 16 bytes (a pool is never copied); strides "
+                         f"{tuple(t.stride())}")
+    if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
+        raise ValueError(f"{what} has stride 0 on a dim larger than 1")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what} is on {t.device}, the layer on {device}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{what} pointer not 16-byte aligned (a pool is never copied)")
+
+
+def _check_scale_pool(what, t, shape=None, device=None, uniform_ok=False):
+    """A float32 scale tensor.  Given `shape`: it is that [num_pages, H, page_size] pool, no
+    stride 0 over a dim larger than 1 (uniform_ok: or it has one element).  Given `device`: it is
+    there, its pointer 4-byte aligned.  `what` names it: "PagedKV: k_scale"."""
+    if shape is not None:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float32, got {t.dtype}")
+        if tuple(t.shape) != tuple(shape) and not (uniform_ok and t.numel() == 1):
+            raise ValueError(f"{what} must {'have one element or ' if uniform_ok else ''}be "
+                             f"[num_pages, H, page_size] = {tuple(shape)}; got {tuple(t.shape)}")
+        if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(t.dim())):
+            raise ValueError(f"{what} has stride 0 on a dim larger than 1 (a scale shared by "
+                             f"several rows cannot follow one of them); strides "
+                             f"{tuple(t.stride())}")
+    if device is not None:
+        if t.device != device:
+            raise ValueError(f"{what} is on {t.device}, the pools on {device}")
+        if t.data_ptr() % 4:
+            raise ValueError(f"{what} pointer not 4-byte aligned")
+
+
 class PagedKV:
     """One layer of a paged cache: pools `[num_pages, H, page_size, D]` (views of any strides
     with a contiguous last dim and 16-byte aligned pointers and strides; never copied), an int32
@@ -87,24 +131,13 @@ class PagedKV:
 
     @staticmethod
     def _check_scale(name, t, k_pool):
-        """A scale tensor against its pools (device and pointer checks: _check_scale_device)."""
+        """A scale tensor against its pools (its device and pointer: the end of __init__)."""
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"PagedKV: {name} must be a tensor, got {type(t).__name__}")
         if not E.is_fp8(k_pool.dtype):
             raise TypeError(f"PagedKV: {name} given with {k_pool.dtype} pools: dequantisation "
                             "scales belong to fp8 (float8_e4m3fn / float8_e5m2) pools")
-        if t.dtype != torch.float32:
-            raise TypeError(f"PagedKV: {name} must be float32, got {t.dtype}")
-        if t.numel() == 1:
-            return
-        npg, H, P, _ = k_pool.shape
-        if tuple(t.shape) != (npg, H, P):
-            raise ValueError(f"PagedKV: {name} must have one element or be [num_pages, H, "
-                             f"page_size] = {(npg, H, P)}; got {tuple(t.shape)}")
-        if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
-            raise ValueError(f"PagedKV: {name} has stride 0 on a dim larger than 1 (a scale "
-                             f"shared by several rows cannot follow one of them); strides "
-                             f"{tuple(t.stride())}")
+        _check_scale_pool(f"PagedKV: {name}", t, k_pool.shape[:3], uniform_ok=True)
 
     def __init__(self, k_pool, v_pool, block_table, seq_len, k_scale=None, v_scale=None):
         for name, t in (("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
@@ -117,10 +150,9 @@ class PagedKV:
             raise ValueError("PagedKV: pools must be bfloat16 / float16 / float32 or fp8 "
                              "(float8_e4m3fn / float8_e5m2) and of one "
                              f"dtype; got {k_pool.dtype} / {v_pool.dtype}")
-        npg, H, P, D = k_pool.shape
-        if npg < 1 or H < 1 or D < 1 or P < 1 or P > 65536 or P & (P - 1):
-            raise ValueError(f"PagedKV: page_size must be a power of two in [1, 65536] and the "
-                             f"pool non-empty; got pools of shape {tuple(k_pool.shape)}")
+        P = k_pool.size(2)
+        _check_pool_view("PagedKV: k_pool", k_pool)
+        _check_pool_view("PagedKV: v_pool", v_pool)
         for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
             if t is not None:
                 self._check_scale(name, t, k_pool)
@@ -129,15 +161,6 @@ class PagedKV:
                              seq_len < 0):
             raise ValueError(f"PagedKV: seq_len must be a non-negative int (or one per sequence), "
                              f"got {seq_len!r}")
-        es = k_pool.element_size()
-        for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
-            if (t.stride(3) != 1 and D > 1) or (D * es) % 16 or any(
-                    (t.stride(d) * es) % 16 and t.size(d) > 1 for d in range(3)):
-                raise ValueError(f"PagedKV: {name} needs a contiguous last dim and rows and "
-                                 f"strides that are multiples of 16 bytes (a pool is never "
-                                 f"copied); strides {tuple(t.stride())}")
-            if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
-                raise ValueError(f"PagedKV: {name} has stride 0 on a dim larger than 1")
         if block_table.dtype != torch.int32 or block_table.dim() != 2 or \
                 (block_table.stride(1) != 1 and block_table.size(1) > 1):
             raise ValueError("PagedKV: block_table must be an int32 [B, pages per sequence] "
@@ -156,18 +179,9 @@ class PagedKV:
             raise ValueError("PagedKV: pools and block table must be on one ROCm device (no CPU "
                              f"fallback); got {k_pool.device} / {v_pool.device} / "
                              f"{block_table.device}")
-        for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
-            if t.data_ptr() % 16:
-                raise ValueError(f"PagedKV: {name} pointer not 16-byte aligned (a pool is never "
-                                 "copied)")
         for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if t is None:
-                continue
-            if t.device != k_pool.device:
-                raise ValueError(f"PagedKV: {name} is on {t.device}, the pools on "
-                                 f"{k_pool.device}")
-            if t.data_ptr() % 4:
-                raise ValueError(f"PagedKV: {name} pointer not 4-byte aligned")
+            if t is not None:
+                _check_scale_pool(f"PagedKV: {name}", t, device=k_pool.device)
         self.k_pool, self.v_pool, self.block_table = k_pool, v_pool, block_table
         self.k_scale, self.v_scale = k_scale, v_scale
         self.seq_len = seq_len if lens is None else lens
@@ -215,39 +229,34 @@ class PagedKV:
     def scales_to_dense(self, n=None, b=None):
         """(K scales, V scales) [B, H, n] of the first n logical rows, by torch indexing, as
         to_dense gives the rows; a uniform scale is expanded, a missing one is None."""
-        if n is None:
-            if b is None and self.ragged:
-                raise ValueError("PagedKV.scales_to_dense: a ragged layer needs b (one sequence) "
-                                 "or n")
-            n = self.seq_len if b is None else self.seq_lens[b]
-        table = self.block_table if b is None else self.block_table[b:b + 1]
-        pos = torch.arange(n, device=self.k_pool.device)
-        pg = table[:, :max(-(-n // self.page_size), 1)].long()
-        pg = pg[:, pos // self.page_size]
-        slot = pos % self.page_size
+        pg, slot = self._page_slot("scales_to_dense", n, b)
         H = self.k_pool.size(1)
 
         def dense(t):
             if t is None:
                 return None
             if t.numel() == 1:
-                return t.reshape(1, 1, 1).expand(table.size(0), H, n)
+                return t.reshape(1, 1, 1).expand(pg.size(0), H, pg.size(1))
             return t[pg, :, slot].permute(0, 2, 1)
         return dense(self.k_scale), dense(self.v_scale)
+
+    def _page_slot(self, who, n, b):
+        """(page [B, n], slot [n]) of the first n logical rows -- by default all of them, or
+        sequence b's -- of every sequence, or of sequence b alone ([1, n])."""
+        if n is None:
+            if b is None and self.ragged:
+                raise ValueError(f"PagedKV.{who}: a ragged layer needs b (one sequence) or n")
+            n = self.seq_len if b is None else self.seq_lens[b]
+        table = self.block_table if b is None else self.block_table[b:b + 1]
+        pos = torch.arange(n, device=self.k_pool.device)
+        pg = table[:, :max(-(-n // self.page_size), 1)].long()
+        return pg[:, pos // self.page_size], pos % self.page_size
 
     def to_dense(self, n=None, b=None):
         """(K, V) [B, H, n, D] of the first n (default seq_len) logical rows, by torch indexing:
         a convenience for tests and debugging, not on the hot path.  With `b`: sequence b's rows
         alone, [1, H, n, D], n by default its own length (a ragged layer needs `b` or `n`)."""
-        if n is None:
-            if b is None and self.ragged:
-                raise ValueError("PagedKV.to_dense: a ragged layer needs b (one sequence) or n")
-            n = self.seq_len if b is None else self.seq_lens[b]
-        table = self.block_table if b is None else self.block_table[b:b + 1]
-        pos = torch.arange(n, device=self.k_pool.device)
-        pg = table[:, :max(-(-n // self.page_size), 1)].long()
-        pg = pg[:, pos // self.page_size]            # [B, n] page of every row
-        slot = pos % self.page_size                  # [n]
+        pg, slot = self._page_slot("to_dense", n, b)
         return tuple(pool[pg, :, slot].permute(0, 2, 1, 3) for pool in (self.k_pool, self.v_pool))
 
 
@@ -310,24 +319,8 @@ class PagedDest:
                                  f"layer's H = {H} and D = {D}, K and V alike; got "
                                  f"{tuple(t.shape)}")
         npg, _, P, _ = kp.shape
-        if npg < 1 or P < 1 or P > 65536 or P & (P - 1):
-            raise ValueError(f"{what}: page_size must be a power of two in [1, 65536] and the "
-                             f"pool non-empty; got pools of shape {tuple(kp.shape)}")
-        es = kp.element_size()
-        for name, t in (("k_pool", kp), ("v_pool", vp)):
-            if (t.stride(3) != 1 and D > 1) or any(
-                    (t.stride(d) * es) % 16 and t.size(d) > 1 for d in range(3)):
-                raise ValueError(f"{what}: {name} needs a contiguous last dim and strides that "
-                                 f"are multiples of 16 bytes (a pool is never copied); strides "
-                                 f"{tuple(t.stride())}")
-            if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
-                raise ValueError(f"{what}: {name} has stride 0 on a dim larger than 1")
-            if t.device != pk.k_pool.device:
-                raise ValueError(f"{what}: {name} is on {t.device}, the layer on "
-                                 f"{pk.k_pool.device}")
-            if t.data_ptr() % 16:
-                raise ValueError(f"{what}: {name} pointer not 16-byte aligned (a pool is never "
-                                 "copied)")
+        _check_pool_view(f"{what}: k_pool", kp, pk.k_pool.device)
+        _check_pool_view(f"{what}: v_pool", vp, pk.k_pool.device)
         # a destination pool: the source's own view, or disjoint from both source pools
         same = []
         for name, t, src in (("K", kp, pk.k_pool), ("V", vp, pk.v_pool)):
@@ -360,19 +353,7 @@ class PagedDest:
                 raise ValueError(f"{what}: {side} given, but the layer's {side} is not per-token "
                                  "(nothing of it moves)")
             if t is not None and t is not src:
-                if t.dtype != torch.float32:
-                    raise TypeError(f"{what}: {side} must be float32, got {t.dtype}")
-                if tuple(t.shape) != (npg, H, P):
-                    raise ValueError(f"{what}: {side} must be [num_pages, H, page_size] = "
-                                     f"{(npg, H, P)}; got {tuple(t.shape)}")
-                if any(t.stride(d) == 0 and t.size(d) > 1 for d in range(3)):
-                    raise ValueError(f"{what}: {side} has stride 0 on a dim larger than 1; "
-                                     f"strides {tuple(t.stride())}")
-                if t.device != pk.k_pool.device:
-                    raise ValueError(f"{what}: {side} is on {t.device}, the pools on "
-                                     f"{pk.k_pool.device}")
-                if t.data_ptr() % 4:
-                    raise ValueError(f"{what}: {side} pointer not 4-byte aligned")
+                _check_scale_pool(f"{what}: {side}", t, (npg, H, P), pk.k_pool.device)
             scales.append(t)
         return PagedDest(bt, kp, vp, *scales)
 
@@ -486,6 +467,61 @@ def _pool_span(t):
     return lo, t.data_ptr() + sum(e for e in ext if e > 0) + t.size(3) * es
 
 
+def _claim_pools(seen, i, pk):
+    """Layer i is compacted in place: its pools are no earlier in-place layer's (`seen`)."""
+    for name, t in (("K", pk.k_pool), ("V", pk.v_pool)):
+        if t.data_ptr() in seen:
+            raise ValueError(f"layer {i}: {name} pool shares its memory with "
+                             f"{seen[t.data_ptr()]}: not compacted in place")
+        seen[t.data_ptr()] = f"layer {i}'s {name} pool"
+
+
+def _check_capacity(i, pd, n):
+    """Layer i's bound PagedDest can address the n rows of its longest result."""
+    if n > pd.capacity:
+        raise ValueError(f"layer {i}: PagedDest block_table {tuple(pd.block_table.shape)} holds "
+                         f"fewer than the {-(-n // pd.page_size)} pages of {n} rows of "
+                         f"{pd.page_size}")
+
+
+def _deferred(raw, kvl, dests, kwargs):
+    """_engine._deferred for a method's own Python over stand-ins (it gets a list of its own)."""
+    return E._deferred(lambda kv: raw(list(kv), **kwargs), kvl, dests)
+
+
+def _launch_rows(pairs):
+    """The numpy rows of a launch group, from the (PagedKV, bound PagedDest or None) of its
+    layers -- a group's layers are all scaled or none is, and all have a PagedDest or none has:
+    (layer table, dict of the pages / scales / pdests / dscales arrays, None where the group has
+    no such table).  Pools, strides and descriptions are filled; k_out / v_out are the
+    destination pools, or the layer's own with in_place = 1.  The segment fields and whatever
+    a dense destination changes are the caller's."""
+    n = len(pairs)
+    sc, repage = pairs[0][0].scaled, pairs[0][1] is not None
+    table = np.zeros(n, dtype=N.LAYER_DTYPE)
+    rows = dict(pages=np.zeros(n, dtype=N.PAGES_DTYPE),
+                scales=np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None,
+                pdests=np.zeros(n, dtype=N.PAGE_DEST_DTYPE) if repage else None,
+                dscales=np.zeros(n, dtype=N.SCALES_DTYPE) if repage and sc else None)
+    for i, (pk, pd) in enumerate(pairs):
+        kp, vp, bt = pk.k_pool, pk.v_pool, pk.block_table
+        t = table[i]
+        t["k"] = t["k_out"] = kp.data_ptr()
+        t["v"] = t["v_out"] = vp.data_ptr()
+        t["k_stride"] = (0, kp.stride(1), kp.stride(2))
+        t["v_stride"] = (0, vp.stride(1), vp.stride(2))
+        rows["pages"][i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
+                            kp.size(0), 0 if repage else 1, 0)
+        if sc:
+            rows["scales"][i] = pk.scales_row()
+        if repage:  # through the destination table: kvc_launch_repage
+            t["k_out"], t["v_out"] = pd.k_pool.data_ptr(), pd.v_pool.data_ptr()
+            rows["pdests"][i] = pd.dest_row()
+            if sc:
+                rows["dscales"][i] = pd.scales_row(rows["scales"][i])
+    return table, rows
+
+
 def compress_paged(method, layers, out="inplace", **kwargs):
     """Run compress method `method` (a name from list_methods(), "evict_for_space", or the
     function) on `layers`, a list of PagedKV, with `kwargs` as the method's keyword arguments.
@@ -561,22 +597,10 @@ def _compress_paged(method, layers, out, kwargs):
         if d != "inplace":
             E._check_dest_tensors(i, k, v, d[0], d[1])
             continue
-        for name, t in (("K", pk.k_pool), ("V", pk.v_pool)):
-            if t.data_ptr() in seen:
-                raise ValueError(f"layer {i}: {name} pool shares its memory with "
-                                 f"{seen[t.data_ptr()]}: not compacted in place")
-            seen[t.data_ptr()] = f"layer {i}'s {name} pool"
+        _claim_pools(seen, i, pk)
     raw = getattr(fn, "__wrapped__", fn)  # the method's own Python: no call memo, no `out`
-    ctx = E._DestCall(dests)
-    prev = getattr(E._dest_state, "ctx", None)
-    try:
-        E._dest_state.ctx = ctx
-        try:
-            res = raw(list(kvl), **kwargs)  # launches nothing: see _engine._defer()
-        finally:
-            E._dest_state.ctx = prev
-        res = list(res)
-        moves = E._dest_moves(kvl, res, dests, ctx)
+    res, moves, ctx = _deferred(raw, kvl, dests, kwargs)
+    with E._rolled_back(ctx):
         every = [j for jobs, _, _ in ctx.pending for j in jobs] + moves
         for j in every:
             pk = layers[j.layer_idx]
@@ -585,20 +609,14 @@ def _compress_paged(method, layers, out, kwargs):
                                    "compress_paged cannot map onto its PagedKV")
             j.paged = pk
             j.page_dest = pdests[j.layer_idx]
-            if j.page_dest is not None and \
-                    j.sink_len + j.n_select + j.tail_len > j.page_dest.capacity:
-                raise ValueError(
-                    f"layer {j.layer_idx}: PagedDest block_table "
-                    f"{tuple(j.page_dest.block_table.shape)} holds fewer than the "
-                    f"{-(-(j.sink_len + j.n_select + j.tail_len) // j.page_dest.page_size)} pages "
-                    f"of {j.sink_len + j.n_select + j.tail_len} rows of "
-                    f"{j.page_dest.page_size}")
-            if j.page_dest is None:  # (a PagedDest's stand-ins say nothing about memory)
+            n = j.sink_len + j.n_select + j.tail_len
+            if j.page_dest is not None:
+                _check_capacity(j.layer_idx, j.page_dest, n)
+            else:  # (a PagedDest's stand-ins say nothing about memory)
                 E._check_dest(j)
             j.dest_verified = True
             E._check_tensors(j)
             if j.page_dest is None and j.k_dest is not j.keys:  # dense: must not meet the pools
-                n = j.sink_len + j.n_select + j.tail_len
                 for name, dst in (("K", j.k_dest), ("V", j.v_dest)):
                     lo, hi = E._span(dst, n)
                     for sname, pool in (("K", pk.k_pool), ("V", pk.v_pool)):
@@ -606,10 +624,6 @@ def _compress_paged(method, layers, out, kwargs):
                         if n and lo < phi and plo < hi:
                             raise ValueError(f"layer {j.layer_idx}: {name} destination overlaps "
                                              f"the layer's {sname} pool")
-    except BaseException:
-        for undo in reversed(ctx.rollback):
-            undo()
-        raise
     scratch = [None] * L
     for _, run, _ in ctx.pending:
         run()  # _engine.execute -> run_jobs
@@ -665,15 +679,8 @@ def _plan_spans(fn, lens, geometry, kwargs, check, unordered=()):
             base, half = bases[(dtype, device)]
             kvl.append((base.as_strided((1, H, S, D), (0, 0, 1, 0), 0),
                         base.as_strided((1, H, S, D), (0, 0, 1, 0), half)))
-        ctx = E._DestCall(dests)
-        prev = getattr(E._dest_state, "ctx", None)
-        try:
-            E._dest_state.ctx = ctx
-            try:
-                res = list(raw(list(kvl), **kwargs))  # launches nothing: see _engine._defer()
-            finally:
-                E._dest_state.ctx = prev
-            moves = E._dest_moves(kvl, res, dests, ctx)
+        res, moves, ctx = _deferred(raw, kvl, dests, kwargs)
+        with E._rolled_back(ctx):
             found = [(j, how) for (jobs, _, _), how in zip(ctx.pending, ctx.how) for j in jobs]
             found += [(j, None) for j in moves]
             done = set()
@@ -705,10 +712,6 @@ def _plan_spans(fn, lens, geometry, kwargs, check, unordered=()):
                     row = new_len[li]
                     for b in bs:
                         row[b] = n
-        except BaseException:
-            for undo in reversed(ctx.rollback):
-                undo()
-            raise
     return rec, spans, new_len
 
 
@@ -731,13 +734,8 @@ def _compress_ragged(fn, layers, dests, kwargs):
         if pk.block_table.size(0) != B:
             raise ValueError(f"layer {i}: {pk.block_table.size(0)} sequences, layer 0 has {B}: the "
                              "layers of a ragged call share one batch")
-        if isinstance(dests[i], PagedDest):  # the pool is only read
-            continue
-        for name, t in (("K", pk.k_pool), ("V", pk.v_pool)):
-            if t.data_ptr() in seen:
-                raise ValueError(f"layer {i}: {name} pool shares its memory with "
-                                 f"{seen[t.data_ptr()]}: not compacted in place")
-            seen[t.data_ptr()] = f"layer {i}'s {name} pool"
+        if not isinstance(dests[i], PagedDest):  # (a PagedDest: the pool is only read)
+            _claim_pools(seen, i, pk)
     pdests = [d.bind(i, pk) if isinstance(d, PagedDest) else None
               for i, (pk, d) in enumerate(zip(layers, dests))]
     rec, spans, new_len = _plan_spans(
@@ -747,11 +745,7 @@ def _compress_ragged(fn, layers, dests, kwargs):
     for li, pd in enumerate(pdests):
         if pd is None:
             continue
-        n = max(new_len[li], default=0)
-        if n > pd.capacity:
-            raise ValueError(f"layer {li}: PagedDest block_table {tuple(pd.block_table.shape)} "
-                             f"holds fewer than the {-(-n // pd.page_size)} pages of {n} rows of "
-                             f"{pd.page_size}")
+        _check_capacity(li, pd, max(new_len[li], default=0))
         # a sequence that no job or move touches passes through (or is already its front view):
         # its destination table must describe it, so its rows are copied
         rest = sorted(set(range(B)) - {b for l2, bs, _ in spans if l2 == li for b in bs})
@@ -797,44 +791,21 @@ def _compress_ragged(fn, layers, dests, kwargs):
         dev[device] = torch.from_numpy(host[device].view(np.uint8)).to(
             torch.device("cuda", device))
     launches = []
-    for (device, dtype, H, D, sc, repage, order, algo), lis, slot in plans:  # plan (and check)
+    for (device, dtype, H, D, _, _, order, algo), lis, slot in plans:  # plan (and check)
         with torch.cuda.device(device):
             p = E._params(dtype, B, H, D, order, algo, False)
-            n = len(lis)
-            table = np.zeros(n, dtype=N.LAYER_DTYPE)
-            pages = np.zeros(n, dtype=N.PAGES_DTYPE)
-            ragged = np.zeros(n, dtype=N.RAGGED_DTYPE)
-            scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
-            pds = np.zeros(n, dtype=N.PAGE_DEST_DTYPE) if repage else None
-            dscales = np.zeros(n, dtype=N.SCALES_DTYPE) if repage and sc else None
+            table, rows = _launch_rows([(layers[li], pdests[li]) for li in lis])
+            ragged = np.zeros(len(lis), dtype=N.RAGGED_DTYPE)
             off = int(start[device][slot])
-            for i, li in enumerate(lis):
-                pk = layers[li]
-                kp, vp, bt = pk.k_pool, pk.v_pool, pk.block_table
-                t = table[i]
-                t["k"] = t["k_out"] = kp.data_ptr()
-                t["v"] = t["v_out"] = vp.data_ptr()
-                t["k_stride"] = (0, kp.stride(1), kp.stride(2))
-                t["v_stride"] = (0, vp.stride(1), vp.stride(2))
-                pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
-                            kp.size(0), 0 if repage else 1, 0)
+            for i in range(len(lis)):  # the layer's B records, on the host and on the device
                 step = off + i * B * N.SEQ_DTYPE.itemsize
                 ragged[i] = (host[device].ctypes.data + step, dev[device].data_ptr() + step)
-                if sc:
-                    scales[i] = pk.scales_row()
-                if repage:
-                    pd = pdests[li]
-                    t["k_out"], t["v_out"] = pd.k_pool.data_ptr(), pd.v_pool.data_ptr()
-                    pds[i] = pd.dest_row()
-                    if sc:
-                        dscales[i] = pd.scales_row(scales[i])
-            ws, info = E._upload(p, table, device, None, B, H, None, pages, ragged, scales, pds,
-                                 dscales)
-            launches.append((device, p, table, ws, info, pages, ragged, scales, pds, dscales))
-    for device, p, table, ws, info, pages, ragged, scales, pds, dscales in launches:
+            tables = N.Tables(ragged=ragged, **rows)
+            ws, info = E._upload(p, table, device, None, B, H, tables)
+            launches.append((device, p, table, ws, info, tables))
+    for device, p, table, ws, info, tables in launches:
         with torch.cuda.device(device):
-            E._launch(p, table, ws, info, torch.cuda.current_stream(device), p.phases, None, pages,
-                      ragged, scales, pds, dscales)
+            E._launch(p, table, ws, info, torch.cuda.current_stream(device), p.phases, tables)
     return new_len
 
 
@@ -853,49 +824,27 @@ def run_jobs(jobs, order, algo):
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device)
             p = E._params(dtype, B, H, D, order, algo, external)
-            n = len(js)
-            table = np.zeros(n, dtype=N.LAYER_DTYPE)
-            pages = np.zeros(n, dtype=N.PAGES_DTYPE)
-            dests = np.zeros(n, dtype=N.DEST_DTYPE)
-            scales = np.zeros(n, dtype=N.SCALES_DTYPE) if sc else None
-            pdests = np.zeros(n, dtype=N.PAGE_DEST_DTYPE) if repage else None
-            dscales = np.zeros(n, dtype=N.SCALES_DTYPE) if repage and sc else None
+            table, rows = _launch_rows([(j.paged, j.page_dest) for j in js])
+            dests = np.zeros(len(js), dtype=N.DEST_DTYPE)
             dense = False
             for i, j in enumerate(js):
-                pk = j.paged
-                kp, vp, bt = pk.k_pool, pk.v_pool, pk.block_table
-                inplace = j.k_dest is j.keys
                 t = table[i]
-                t["k"], t["v"] = kp.data_ptr(), vp.data_ptr()
-                t["k_stride"] = (0, kp.stride(1), kp.stride(2))
-                t["v_stride"] = (0, vp.stride(1), vp.stride(2))
-                t["seq_len"], t["zone_start"], t["zone_len"] = pk.seq_len, j.zone_start, j.zone_len
+                t["seq_len"], t["zone_start"], t["zone_len"] = j.paged.seq_len, j.zone_start, \
+                    j.zone_len
                 t["n_select"], t["sink_len"] = j.n_select, j.sink_len
                 t["tail_start"], t["tail_len"] = j.tail_start, j.tail_len
                 t["pool_kernel"], t["score_mode"] = j.pool_kernel, j.score_mode
-                pages[i] = (bt.data_ptr(), bt.stride(0), kp.stride(0), vp.stride(0), kp.size(2),
-                            kp.size(0), 1 if inplace else 0, 0)
-                if sc:
-                    if not inplace and not repage:  # (compress_paged refuses it before planning)
-                        raise TypeError("a scaled layer is compacted in place only")
-                    scales[i] = pk.scales_row()
-                if repage:  # through the destination table: kvc_launch_repage
-                    pd = j.page_dest
-                    t["k_out"], t["v_out"] = pd.k_pool.data_ptr(), pd.v_pool.data_ptr()
-                    pdests[i] = pd.dest_row()
-                    if sc:
-                        dscales[i] = pd.scales_row(scales[i])
-                elif inplace:
-                    t["k_out"], t["v_out"] = t["k"], t["v"]
-                else:
-                    dense = True
-                    t["k_out"], t["v_out"] = j.k_dest.data_ptr(), j.v_dest.data_ptr()
-                    dests[i] = (j.k_dest.stride()[:3], j.v_dest.stride()[:3], 0, 0)
-            dd = dests if dense else None
-            ws, info = E._upload(p, table, device, js, B, H, dd, pages, None, scales, pdests,
-                                 dscales)
-            E._launch(p, table, ws, info, stream, p.phases, dd, pages, None, scales, pdests,
-                      dscales)
+                if repage or j.k_dest is j.keys:
+                    continue
+                if sc:  # (compress_paged refuses it before planning)
+                    raise TypeError("a scaled layer is compacted in place only")
+                dense = True  # a dense destination: the pool is only read
+                rows["pages"]["in_place"][i] = 0
+                t["k_out"], t["v_out"] = j.k_dest.data_ptr(), j.v_dest.data_ptr()
+                dests[i] = (j.k_dest.stride()[:3], j.v_dest.stride()[:3], 0, 0)
+            tables = N.Tables(dests=dests if dense else None, **rows)
+            ws, info = E._upload(p, table, device, js, B, H, tables)
+            E._launch(p, table, ws, info, stream, p.phases, tables)
 
 
 __all__ = ["PagedKV", "PagedDest", "compress_paged", "check_repage_tables"]

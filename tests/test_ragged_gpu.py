@@ -37,6 +37,14 @@ def test_every_method(method, kw, L, geo):
         assert lens[l][0] == 0 and lens[l][1] == 37
 
 
+def test_33_layers_cross_the_argument_chunk():
+    """33 ragged layers in one launch: the argument chunk of a paged launch holds 32."""
+    kw = dict(fix_kv_size=48, keep_ratio=0.25, skip_layers=[])
+    layers_np, pls = RU.build(4200, [100, 37], 2, 32, "bf16", 16, 33)
+    lens, _ = RU.check_against_oracle("fix_size_l2", kw, layers_np, pls, ("33 layers",))
+    assert lens == [[48, 37]] * 33
+
+
 def test_lengths_given_as_array_and_tensor():
     """numpy and CPU-tensor lengths, an int layer beside ragged ones (B equal lengths), and
     to_dense(b=...) of the compacted rows."""

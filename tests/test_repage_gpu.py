@@ -492,6 +492,55 @@ def test_scaled_17_layers_cross_the_scale_carrying_chunk():
         pool.assert_pools(snap, ("17 layers", li))
 
 
+def test_ragged_33_layers_cross_the_argument_chunk():
+    """33 ragged layers through destination tables in one launch: the argument chunk holds 32."""
+    from kvcompress import compress_paged
+    kw = dict(fix_kv_size=48, keep_ratio=0.25, skip_layers=[])
+    lens = [100, 37]
+    layers_np, pls, dsts = _ragged_setup(45000, lens, 32, "bf16", 16, 33, ("nhpd", "nphd"), 48,
+                                         True)
+    ref = RU.oracle_per_sequence("fix_size_l2", kw, layers_np)
+    snaps = [d.snapshot() for d in dsts]
+    got = compress_paged("fix_size_l2", [pl.paged for pl in pls],
+                         out=[d.paged_dest() for d in dsts], **kw)
+    torch.cuda.synchronize()
+    for l in range(33):
+        assert list(got[l]) == [48, 37], (l, got[l])
+        for b in range(len(lens)):
+            rk, rv, kind = ref[l][b]
+            rk, rv = layers_np[l][b] if kind == "same" else (rk, rv)
+            dsts[l].expect(snaps[l], rk, rv, b)
+        dsts[l].assert_pools(snaps[l], ("ragged 33 layers", l))
+
+
+def test_ragged_scaled_17_layers_cross_the_scale_carrying_chunk():
+    """17 ragged scale-carrying layers in one launch: the argument chunk of that copy holds 16.
+    (D = 64: the narrowest fp8 row.)"""
+    import fp8_gpu as G
+    import scaled_gpu as SG
+    import scaled_util as SU
+    from kvcompress import compress_paged
+    from test_scaled_methods_gpu import _ragged_expect
+    fmt, D, kw = "e5m2", 64, dict(SU.KWARGS["fix_size_l2"], fix_kv_size=48)
+    lens, new = (100, 37), [48, 37]
+    layers = [[SU.method_layer(99500 + 100 * l + b, n, D, fmt) for b, n in enumerate(lens)]
+              for l in range(17)]
+    pos = _ragged_expect("fix_size_l2", kw, layers, fmt)
+    with RP.spare(RP.pages_for(new, 16)):
+        pools = [SG.ScaledPool(l, fmt, 16, 99600 + i, G.STORAGES[i % 2], SG.SCALE_STORAGES[i % 2])
+                 for i, l in enumerate(layers)]
+    dsts = [_scaled_dest(p, new, 99600 + i) for i, p in enumerate(pools)]
+    snaps = [p.snapshot() for p in pools]
+    got = compress_paged("fix_size_l2", [p.paged(ragged=True) for p in pools],
+                         out=[d.paged_dest() for d in dsts], **kw)
+    torch.cuda.synchronize()
+    for l, (pool, d, snap) in enumerate(zip(pools, dsts, snaps)):
+        assert list(got[l]) == new == [p_.shape[2] for p_ in pos[l]]
+        for b, p_ in enumerate(pos[l]):
+            _scaled_expect(pool, d, snap, b, SU.expected_layer(p_, *layers[l][b]))
+        pool.assert_pools(snap, ("ragged 17 layers", l))
+
+
 # ---- 8 (phases), 9, 10, 11: the C ABI's promises on the new copy kernels -----------------------
 def _fields(s):
     """kvc_layer_t segment fields of a phase_tables spec."""

@@ -92,6 +92,16 @@ def test_fix_size_l2_other_page_sizes(fmt, P):
                           _pools(layers, fmt, P, 93500 + P), fmt, ("fix_size_l2", fmt, D, P))
 
 
+def test_33_layers_cross_the_argument_chunk():
+    """33 scaled layers compacted in place in one launch: the argument chunk of a paged launch
+    holds 32.  (D = 64: the narrowest fp8 row.)"""
+    fmt, D, kw = "e4m3", 64, dict(SU.KWARGS["fix_size_l2"], fix_kv_size=48)
+    layers = SU.method_layers(92700, D, fmt, lens=(100,) * 33)
+    lens, _, moved = _expect_and_check("fix_size_l2", kw, layers, _pools(layers, fmt, 16, 93700),
+                                       fmt, ("33 layers",))
+    assert list(lens) == [48] * 33 and moved
+
+
 def _ragged_layers(seed, D, fmt, n_layers=2):
     return [[SU.method_layer(seed + 100 * l + b, n, D, fmt) for b, n in enumerate(SU.RAGGED_LENS)]
             for l in range(n_layers)]
