@@ -42,6 +42,7 @@
 #include "kvc_paged.h"          // score_paged_kernel, gather_paged_kernel (kvc_launch_paged)
 #include "kvc_ragged.h"         // the per-sequence-record kernels (kvc_launch_ragged)
 #include "kvc_repage.h"         // GATHER through a destination block table (kvc_launch_repage)
+#include "kvc_observe.h"        // observation-window scores on the MFMA units (kvc_observe_score)
 
 namespace kvc {
 
@@ -1096,6 +1097,122 @@ static int debug_select_impl(const kvc_params_t* p, const kvc_layer_t* layers, i
   });
 }
 
+// ---- observation-window scores (kvc_observe.h) ----------------------------------------------
+// Scratch of kvc_observe_score: the statistics partials [rows][pstride][32] float2, then the
+// column sums [rows][istride] fp32; strides by the longest scored layer and zone.
+struct ObserveLayout {
+  int64_t pstride, istride, max_seq, max_zone;
+  size_t part_bytes, total;
+};
+
+// include/kvc.h, "Observation-window scores": the rules of a call on a planned table.
+static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* op,
+                             const kvc_layer_t* layers, const kvc_observe_layer_t* ol, int nl,
+                             kvc_plan_info_t* info, ObserveLayout* lay) {
+  if (!p || !op || nl < 0 || (nl > 0 && (!layers || !ol))) return KVC_E_ARG;
+  int rc = plan_impl(p, const_cast<kvc_layer_t*>(layers), nl, info, false);
+  if (rc != KVC_OK) return rc;
+  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16) return KVC_E_DTYPE;
+  if (p->head_dim != 64 && p->head_dim != 128 && p->head_dim != 256) return KVC_E_HEADDIM;
+  if (p->external_index) return KVC_E_ARG;
+  const int W = op->window;
+  if (W != 16 && W != 32 && W != 64) return KVC_E_ARG;
+  if (op->q_heads < p->heads || op->q_heads % p->heads) return KVC_E_ARG;
+  const int G = op->q_heads / p->heads;
+  if ((G != 1 && G != 2 && G != 4 && G != 8) || G * W > kObsMaxM) return KVC_E_ARG;
+  if (op->pool_kernel < 1 || op->pool_kernel > 7 || !(op->pool_kernel & 1)) return KVC_E_ARG;
+  if (op->pool_mode != KVC_OBS_POOL_AVG && op->pool_mode != KVC_OBS_POOL_MAX) return KVC_E_ARG;
+  if (op->reserved != 0 || !(op->scale - op->scale == 0.f)) return KVC_E_ARG;  // finite
+  lay->max_seq = lay->max_zone = 0;
+  for (int l = 0; l < nl; ++l) {
+    const kvc_layer_t& y = layers[l];
+    const kvc_observe_layer_t& q = ol[l];
+    if (y.score_mode != KVC_SCORE_NORM || q.reserved != 0) return KVC_E_ARG;
+    if (y.zone_len == 0) continue;
+    if (y.seq_len < W + 1 || (int64_t)y.zone_start + y.zone_len > y.seq_len - W) return KVC_E_ARG;
+    if (!y.k || !q.q) return KVC_E_ARG;
+    if (!aligned16(y.k) || !aligned16(q.q)) return KVC_E_ALIGN;
+    if ((p->batch > 1 && ((y.k_stride[0] * 2) % 16 || (q.q_stride[0] * 2) % 16)) ||
+        (p->heads > 1 && (y.k_stride[1] * 2) % 16) || (op->q_heads > 1 && (q.q_stride[1] * 2) % 16) ||
+        (y.k_stride[2] * 2) % 16 || (q.q_stride[2] * 2) % 16)
+      return KVC_E_ALIGN;
+    lay->max_seq = y.seq_len > lay->max_seq ? y.seq_len : lay->max_seq;
+    lay->max_zone = y.zone_len > lay->max_zone ? y.zone_len : lay->max_zone;
+  }
+  lay->pstride = (lay->max_seq + kObsChunk - 1) / kObsChunk * kObsWaves;
+  lay->istride = (int64_t)round_up((size_t)lay->max_zone, kTile);
+  lay->part_bytes = round_up((size_t)info->rows * lay->pstride * 32 * sizeof(float2), 256);
+  lay->total = lay->part_bytes + (size_t)info->rows * lay->istride * sizeof(float);
+  return KVC_OK;
+}
+
+// The three kernels of one chunk of <= kObsLayers layers, grids by the chunk's longest layer.
+template <int DT, int NC>
+static int launch_observe_chunk(const ObserveChunk& C, const ObserveArgs& A, int cn, int max_seq,
+                                int max_zone, hipStream_t s) {
+  const unsigned rows = (unsigned)(cn * A.BH);
+  const dim3 pass_grid(rows, (unsigned)((max_seq + kObsChunk - 1) / kObsChunk));
+  int rc = launch_k(observe_pass_kernel<DT, NC, 1, false>, pass_grid, dim3(kObsThreads), 0, s, C, A);
+  if (rc != KVC_OK) return rc;
+  rc = launch_k(observe_pass_kernel<DT, NC, 2, kObsPass2NT>, pass_grid, dim3(kObsThreads), 0, s,
+                C, A);
+  if (rc != KVC_OK) return rc;
+  return launch_k(observe_pool_kernel<DT>,
+                  dim3(rows, (unsigned)((max_zone + kPoolThreads - 1) / kPoolThreads)),
+                  dim3(kPoolThreads), 0, s, C, A);
+}
+
+static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t* op,
+                              const kvc_layer_t* layers, const kvc_observe_layer_t* ol, int nl,
+                              char* w, size_t wbytes, char* scratch, size_t sbytes, float* f32,
+                              hipStream_t s) {
+  kvc_plan_info_t info;
+  ObserveLayout lay;
+  int rc = observe_plan_impl(p, op, layers, ol, nl, &info, &lay);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0 || lay.max_zone == 0) return KVC_OK;
+  if (!w || wbytes < info.workspace_bytes || !scratch || sbytes < lay.total) return KVC_E_WORKSPACE;
+  if (!aligned16(scratch) || ((uintptr_t)f32 & 3u)) return KVC_E_ALIGN;
+  if (f32 && op->scores_row_stride < lay.max_zone) return KVC_E_ARG;
+  ObserveArgs A;
+  A.H = p->heads, A.BH = p->batch * p->heads;
+  A.G = op->q_heads / p->heads, A.W = op->window, A.M = A.G * A.W, A.MB = (A.M + 31) / 32;
+  const float scale = op->scale != 0.f ? op->scale : 1.f / __builtin_sqrtf((float)p->head_dim);
+  A.scale2 = scale * 1.44269504088896340736f;
+  A.pool = op->pool_kernel, A.pool_max = op->pool_mode == KVC_OBS_POOL_MAX;
+  A.nstride = info.norm_row_stride, A.pstride = lay.pstride, A.istride = lay.istride;
+  A.fstride = op->scores_row_stride;
+  A.part = reinterpret_cast<float2*>(scratch);
+  A.imp = reinterpret_cast<float*>(scratch + lay.part_bytes);
+  A.norms = w + info.norm_offset, A.f32 = f32;
+  const int nc = p->head_dim * 2 / 16;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kObsLayers) {
+    const int cn = nl - c0 < kObsLayers ? nl - c0 : kObsLayers;
+    ObserveChunk C;
+    memset(&C, 0, sizeof(C));
+    memcpy(C.l, layers + c0, (size_t)cn * sizeof(kvc_layer_t));
+    memcpy(C.q, ol + c0, (size_t)cn * sizeof(kvc_observe_layer_t));
+    int max_seq = 0, max_zone = 0;
+    for (int l = 0; l < cn; ++l) {
+      if (!observe_scored(C.l[l], f32 != nullptr)) continue;
+      max_seq = C.l[l].seq_len > max_seq ? C.l[l].seq_len : max_seq;
+      max_zone = C.l[l].zone_len > max_zone ? C.l[l].zone_len : max_zone;
+    }
+    if (max_zone == 0) continue;
+    const auto go = [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      switch (nc) {
+        case 8: return launch_observe_chunk<DT, 8>(C, A, cn, max_seq, max_zone, s);
+        case 16: return launch_observe_chunk<DT, 16>(C, A, cn, max_seq, max_zone, s);
+        default: return launch_observe_chunk<DT, 32>(C, A, cn, max_seq, max_zone, s);
+      }
+    };
+    rc = p->dtype == KVC_BF16 ? go(std::integral_constant<int, KVC_BF16>())
+                              : go(std::integral_constant<int, KVC_F16>());
+  }
+  return rc;
+}
+
 // ---- h2o_attention host side ----------------------------------------------------------------
 static int attn_params_check(const kvc_attn_params_t* p, bool accumulate = false) {
   if (!p) return KVC_E_ARG;
@@ -1350,6 +1467,27 @@ int kvc_debug_select_capacity(const kvc_params_t* params, const kvc_layer_t* lay
                               int zone_cap, kvc_stream_t stream) {
   return kvc::debug_select_impl(params, layers, num_layers, static_cast<char*>(workspace),
                                 workspace_bytes, zone_cap, reinterpret_cast<hipStream_t>(stream));
+}
+
+int kvc_observe_plan(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                     const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                     int num_layers, size_t* scratch_bytes) {
+  kvc_plan_info_t info;
+  kvc::ObserveLayout lay;
+  if (!scratch_bytes) return KVC_E_ARG;
+  const int rc = kvc::observe_plan_impl(params, oparams, layers, olayers, num_layers, &info, &lay);
+  if (rc == KVC_OK) *scratch_bytes = lay.total;
+  return rc;
+}
+
+int kvc_observe_score(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                      const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                      int num_layers, void* workspace, size_t workspace_bytes, void* scratch,
+                      size_t scratch_bytes, float* scores_f32, kvc_stream_t stream) {
+  return kvc::observe_score_impl(params, oparams, layers, olayers, num_layers,
+                                 static_cast<char*>(workspace), workspace_bytes,
+                                 static_cast<char*>(scratch), scratch_bytes, scores_f32,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 int kvc_attn_accumulate(const kvc_attn_params_t* params, const kvc_attn_layer_t* layers,

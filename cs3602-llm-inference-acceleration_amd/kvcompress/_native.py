@@ -85,6 +85,11 @@ PAGE_DEST_DTYPE = np.dtype([
 ])
 assert PAGE_DEST_DTYPE.itemsize == 72
 
+# struct kvc_observe_layer (include/kvc.h: observation-window scores) -- 40 bytes
+OBSERVE_LAYER_DTYPE = np.dtype([("q", "<u8"), ("q_stride", "<i8", (3,)), ("reserved", "<i8")])
+assert OBSERVE_LAYER_DTYPE.itemsize == 40
+OBS_POOL_AVG, OBS_POOL_MAX = 0, 1  # enum kvc_observe_pool
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -112,6 +117,13 @@ class AttnParams(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("device_status", ctypes.c_void_p)]
 
 
+class ObserveParams(ctypes.Structure):
+    _fields_ = [("q_heads", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("pool_kernel", ctypes.c_int32),
+                ("pool_mode", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("scores_row_stride", ctypes.c_int64)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("norm_offset", ctypes.c_size_t),
                 ("index_offset", ctypes.c_size_t), ("workspace_bytes", ctypes.c_size_t),
@@ -125,7 +137,8 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_plan", "kvc_launch", "kvc_compress", "kvc_attn_accumulate", "kvc_hh_workspace",
            "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
            "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged",
-           "kvc_plan_scaled", "kvc_launch_scaled", "kvc_plan_repage", "kvc_launch_repage")
+           "kvc_plan_scaled", "kvc_launch_scaled", "kvc_plan_repage", "kvc_launch_repage",
+           "kvc_observe_plan", "kvc_observe_score")
 
 _lib = None
 
@@ -193,6 +206,13 @@ def lib():
         L.kvc_launch_repage.restype = i32
         L.kvc_launch_repage.argtypes = [ctypes.POINTER(Params), vp, vp, vp, vp, vp, vp, i32, vp,
                                         ctypes.c_size_t, vp]
+    if hasattr(L, "kvc_observe_plan"):  # additive within ABI 4, like the repage entries
+        L.kvc_observe_plan.restype = i32
+        L.kvc_observe_plan.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(ObserveParams), vp,
+                                       vp, i32, ctypes.POINTER(ctypes.c_size_t)]
+        L.kvc_observe_score.restype = i32
+        L.kvc_observe_score.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(ObserveParams), vp,
+                                        vp, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -380,6 +400,34 @@ def launch_repage(params, table, pages, ragged, scales, pdests, dscales, ws_ptr,
                                    _opt(scales, SCALES_DTYPE, n),
                                    _opt(pdests, PAGE_DEST_DTYPE, n),
                                    _opt(dscales, SCALES_DTYPE, n), n, ws_ptr, ws_bytes, stream_ptr)
+
+
+def _need_observe_entries():
+    if not hasattr(lib(), "kvc_observe_plan"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_observe_plan / kvc_observe_score (built "
+                                 "before observation-window scores); they need the current library")
+
+
+def observe_plan(params, oparams, table, otable):
+    """kvc_observe_plan on a table kvc_plan has filled: (rc, scratch bytes).  `otable` is an
+    OBSERVE_LAYER_DTYPE array, one entry per layer."""
+    assert otable.dtype == OBSERVE_LAYER_DTYPE and len(otable) == len(table)
+    _need_observe_entries()
+    n = ctypes.c_size_t()
+    rc = lib().kvc_observe_plan(ctypes.byref(params), ctypes.byref(oparams), table.ctypes.data,
+                                otable.ctypes.data, len(table), ctypes.byref(n))
+    return rc, n.value
+
+
+def observe_score(params, oparams, table, otable, ws_ptr, ws_bytes, scratch_ptr, scratch_bytes,
+                  f32_ptr, stream_ptr):
+    """kvc_observe_score: fills the norm rows of the planned workspace (f32_ptr: None or the
+    address of the fp32 score rows, oparams.scores_row_stride floats apart)."""
+    assert otable.dtype == OBSERVE_LAYER_DTYPE and len(otable) == len(table)
+    _need_observe_entries()
+    return lib().kvc_observe_score(ctypes.byref(params), ctypes.byref(oparams), table.ctypes.data,
+                                   otable.ctypes.data, len(table), ws_ptr, ws_bytes, scratch_ptr,
+                                   scratch_bytes, f32_ptr, stream_ptr)
 
 
 class Tables:

@@ -220,8 +220,8 @@ const char* kvc_status_string(int status);
 /* SHA-256 (hex) of the sources this library was compiled from (csrc/kvc.hip, then the headers it
  * includes -- kvc_common.h, kvc_serial.h, kvc_device_util.h, kvc_score.h, kvc_snapkv_keys.h,
  * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h,
- * kvc_paged.h, kvc_ragged.h -- then include/kvc.h, in that order), or "unknown" for builds that
- * do not set it --
+ * kvc_paged.h, kvc_ragged.h, kvc_repage.h, kvc_observe.h -- then include/kvc.h, in that order), or
+ * "unknown" for builds that do not set it --
  * lets a caller (and tests/test_abi.py) check that a shipped binary matches its source tree. */
 const char* kvc_source_digest(void);
 
@@ -619,6 +619,83 @@ int kvc_launch_repage(const kvc_params_t* params, const kvc_layer_t* layers,
                       const kvc_scales_t* scales, const kvc_page_dest_t* pdests,
                       const kvc_scales_t* dscales, int num_layers, void* workspace,
                       size_t workspace_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Observation-window scores (SnapKV; additive within ABI 4: no existing struct, size or entry
+ * changes; a library without these two entries does not export them).
+ *
+ * kvc_observe_score stands in for KVC_PHASE_SCORE: it ranks the zone keys of every layer by how
+ * much the layer's last W queries (the observation window, positions S-W .. S-1, post-RoPE) attend
+ * to them, and stores that score where SELECT's KVC_SCORE_NORM contract (top of this file) lets a
+ * caller fill the norm region.  The caller then runs kvc_launch with phases = SELECT | GATHER
+ * (KVC_DESC with KVC_ALGO_TOPK or KVC_ALGO_STABLE keeps the highest scores).  No attention tensor
+ * exists at any point: the kernels read K twice and Q_obs [batch, q_heads, W, head_dim].
+ *
+ * Arithmetic, in fp32 (q_heads = G * heads; query head h*G + g belongs to KV head h):
+ *     s[g,i,j]   = scale * sum_d q[b,h*G+g,i,d] * k[b,h,j,d]          j in [0, S)
+ *     allowed    : j <= S - W + i                                     (causal inside the window)
+ *     p[g,i,j]   = softmax of s over the allowed j (the window's own keys included)
+ *     imp[b,h,j] = sum_g sum_i p[g,i,j]                               j in the zone
+ *     score[j]   = pool(imp)[j]: kernel P, stride 1, padding P/2 INSIDE the zone --
+ *                  KVC_OBS_POOL_AVG: window sum / P with the zero padding counted
+ *                  (avg_pool1d's default); KVC_OBS_POOL_MAX: window maximum
+ * score is rounded to nearest even to the call's dtype and stored at column j - zone_start of row
+ * layer.row0 + b*heads + h of the norm region, for every layer that selects
+ * (0 < n_select < zone_len).  With scores_f32 != NULL the un-rounded fp32 scores of EVERY layer
+ * with zone_len > 0 also go to scores_f32[(layer.row0 + b*heads + h) * scores_row_stride +
+ * j - zone_start] (device memory, 4-byte aligned).
+ * There is no reference counterpart: the contract is numerical (the MFMA accumulation order and
+ * the split of the softmax sums are the library's), not bit-exact; the scores are deterministic --
+ * the same call gives the same bits.  Non-finite K or Q give unspecified scores and nothing else:
+ * no loop or address of the kernels depends on data.
+ *
+ * Rules.  dtype is KVC_BF16 or KVC_F16, Q's dtype too (else KVC_E_DTYPE: fp32 and fp8 keys have no
+ * matrix path here); head_dim is 64, 128 or 256 (KVC_E_HEADDIM); window is 16, 32 or 64, q_heads
+ * = G * heads with G in {1, 2, 4, 8} and G * window <= 128, pool_kernel is 1, 3, 5 or 7,
+ * pool_mode a kvc_observe_pool, scale finite (0 = the default 1/sqrt(head_dim)), reserved fields 0,
+ * external_index 0 (KVC_E_ARG).  Every layer carries score_mode = KVC_SCORE_NORM (KVC_E_ARG).  A
+ * layer with zone_len > 0 has seq_len >= window + 1 and zone_start + zone_len <= seq_len - window
+ * (KVC_E_ARG), k and q non-NULL (KVC_E_ARG) and 16-byte aligned, the strides of K's and Q's dims
+ * larger than 1 multiples of 16 bytes, last dims contiguous (KVC_E_ALIGN).  K / V are dense
+ * (kvc_layer_t's strides): there is no entry with page, ragged or scale tables.
+ *
+ * Launch discipline: three kernels per chunk of 32 layers (statistics, column sums, pooling),
+ * every table by value in the kernel arguments; no allocation, synchronisation or global state.
+ * ------------------------------------------------------------------------------------------- */
+enum kvc_observe_pool { KVC_OBS_POOL_AVG = 0, KVC_OBS_POOL_MAX = 1 };
+
+typedef struct kvc_observe_layer {
+  const void* q;       /* [batch, q_heads, window, head_dim] of the call's dtype */
+  int64_t q_stride[3]; /* element strides of dims batch, q_heads, window         */
+  int64_t reserved;    /* 0                                                      */
+} kvc_observe_layer_t; /* 40 bytes */
+
+typedef struct kvc_observe_params {
+  int32_t q_heads;           /* G * params.heads                                  */
+  int32_t window;            /* W: 16, 32 or 64                                   */
+  float scale;               /* softmax scale; 0 = 1/sqrt(head_dim)               */
+  int32_t pool_kernel;       /* P: 1, 3, 5 or 7                                   */
+  int32_t pool_mode;         /* enum kvc_observe_pool                             */
+  int32_t reserved;          /* 0                                                 */
+  int64_t scores_row_stride; /* floats per row of scores_f32, >= the longest zone
+                                (read only when scores_f32 != NULL)               */
+} kvc_observe_params_t;      /* 32 bytes */
+
+/* Validates the rules above on a table that kvc_plan has filled (same params) and reports the
+ * scratch kvc_observe_score needs: the per-chunk softmax statistics and the fp32 column sums.
+ * Pure host function. */
+int kvc_observe_plan(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                     const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                     int num_layers, size_t* scratch_bytes);
+
+/* Re-validates, launches the kernel set on `stream` and fills the norm rows of the planned
+ * `workspace` (kvc_plan's, at least its workspace_bytes).  `scratch` is device memory, 16-byte
+ * aligned, of at least kvc_observe_plan's scratch_bytes; it needs no initialisation and is free
+ * again when the kernels have run.  scores_f32 may be NULL. */
+int kvc_observe_score(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                      const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                      int num_layers, void* workspace, size_t workspace_bytes, void* scratch,
+                      size_t scratch_bytes, float* scores_f32, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |

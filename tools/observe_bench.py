@@ -1,0 +1,131 @@
+"""What the observation-window score costs ("Observation-window scores"):
+32 layers of [1, Hkv, 16384, 128] bf16 with W = 32, keep 512, for Hkv = 32 (G = 1, the headline
+geometry) and Hkv = 8 with G = 4 (one GQA point, 32 query heads).  In one process, alternating
+over `--rounds` rounds, per geometry:
+  observe_ms   the kvc_observe_score launch set alone (three kernels), `reps` launches between
+               two device events, per launch;
+  score_ms     the existing SCORE kernel (key norms) over the same keys: the bytes-equivalent
+               floor, one read of K;
+  call_ms      the whole snapkv_compress call (plan, observe, SELECT | GATHER, allocations);
+  torch_ms     the same scores outside HIP: matmul -> masked softmax -> sum -> avg_pool1d per layer.
+`read_rate_vs_score` = score_ms / (observe_ms / 2): the rate at which each of the two passes
+reads K, as a fraction of SCORE's; above 1 the second pass was served from cache.
+KVC_LIB=<variant libkvc.so> measures a variant build (e.g. non-temporal pass-2 loads).
+GPU box only.
+
+  python tools/observe_bench.py [--layers 32] [--seq 16384] [--rounds 5] [--reps 10] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cs3602-llm-inference-acceleration_amd"))
+from kvcompress import _engine as E  # noqa: E402
+from kvcompress import _native as N  # noqa: E402
+from kvcompress import snapkv_compress  # noqa: E402
+
+DEV = torch.device("cuda:0")
+D, W, KEEP, POOL = 128, 32, 512, 5
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def torch_scores(kv, qs, G):
+    out = []
+    for (k, _), q in zip(kv, qs):
+        B, H, S, _ = k.shape
+        s = torch.matmul(q.view(B, H, G * W, D), k.transpose(2, 3)).float() * D ** -0.5
+        i = torch.arange(W, device=DEV).repeat(G)
+        s.masked_fill_(torch.arange(S, device=DEV)[None, :] > (S - W + i)[:, None], float("-inf"))
+        imp = torch.softmax(s, -1).sum(2)[:, :, :S - W]
+        out.append(F.avg_pool1d(imp, POOL, 1, POOL // 2))
+    return out
+
+
+def geometry(name, L, S, Hkv, G, rounds, reps, gen):
+    kv = [tuple(torch.empty(1, Hkv, S, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+                for _ in range(2)) for _ in range(L)]
+    qs = [torch.empty(1, G * Hkv, W, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+          for _ in range(L)]
+    # the launch set alone: the table snapkv_compress would plan, launched by hand
+    jobs = [E.Segments(i, k, v, zone_len=S - W, n_select=KEEP - W, tail_start=S - W, tail_len=W)
+            for i, (k, v) in enumerate(kv)]
+    p = E._params(torch.bfloat16, 1, Hkv, D, N.KVC_DESC, N.KVC_ALGO_TOPK, False)
+    table, kos, vos, _ = E._build_table(0, torch.bfloat16, 1, Hkv, D, jobs)
+    rc, info = N.plan(p, table)
+    N.check(rc, "kvc_plan")
+    otable = np.zeros(L, dtype=N.OBSERVE_LAYER_DTYPE)
+    for i, q in enumerate(qs):
+        otable[i] = (q.data_ptr(), q.stride()[:3], 0)
+    op = N.ObserveParams(q_heads=G * Hkv, window=W, pool_kernel=POOL, pool_mode=N.OBS_POOL_AVG)
+    rc, sbytes = N.observe_plan(p, op, table, otable)
+    N.check(rc, "kvc_observe_plan")
+    ws = torch.empty(int(info.workspace_bytes), dtype=torch.uint8, device=DEV)
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def observe():
+        N.check(N.observe_score(p, op, table, otable, ws.data_ptr(), int(info.workspace_bytes),
+                                scratch.data_ptr(), sbytes, None, stream), "kvc_observe_score")
+
+    def score():
+        p.phases = N.PHASE_SCORE
+        N.check(N.launch(p, table, ws.data_ptr(), int(info.workspace_bytes), stream), "kvc_launch")
+
+    runs = {"observe_ms": observe, "score_ms": score,
+            "call_ms": lambda: snapkv_compress(kv, qs, W, KEEP, POOL),
+            "torch_ms": lambda: torch_scores(kv, qs, G)}
+    for fn in runs.values():  # warm-up: code objects, allocator pools
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(rounds):  # alternating
+        for key, fn in runs.items():
+            times[key].append(timed(fn, reps if key != "torch_ms" else 2))
+    rec = {"geometry": name, "layers": L, "seq": S, "kv_heads": Hkv, "group": G, "window": W,
+           "k_bytes": L * Hkv * S * D * 2, "scratch_bytes": sbytes,
+           "lib": os.path.basename(N.LIB_PATH)}
+    for key, v in times.items():
+        rec[key] = round(statistics.median(v), 4)
+        rec[key + "_min_max"] = [round(min(v), 4), round(max(v), 4)]
+    rec["read_rate_vs_score"] = round(rec["score_ms"] / (rec["observe_ms"] / 2), 3)
+    rec["observe_gbps_two_reads"] = round(2 * rec["k_bytes"] / rec["observe_ms"] / 1e6, 1)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--seq", type=int, default=16384)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("observe_bench needs the GPU")
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    lines = [json.dumps(geometry(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen))
+             for n, h, g in (("mha_h32", 32, 1), ("gqa_h8_g4", 8, 4))]
+    print("\n".join(lines))
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
