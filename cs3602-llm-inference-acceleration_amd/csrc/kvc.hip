@@ -43,6 +43,7 @@
 #include "kvc_ragged.h"         // the per-sequence-record kernels (kvc_launch_ragged)
 #include "kvc_repage.h"         // GATHER through a destination block table (kvc_launch_repage)
 #include "kvc_observe.h"        // observation-window scores on the MFMA units (kvc_observe_score)
+#include "kvc_observe_src.h"    // ... of paged and fp8 keys (kvc_observe_score_paged)
 
 namespace kvc {
 
@@ -1105,14 +1106,19 @@ struct ObserveLayout {
   size_t part_bytes, total;
 };
 
-// include/kvc.h, "Observation-window scores": the rules of a call on a planned table.
+// include/kvc.h, "Observation-window scores": the rules of a call on a planned table.  sources:
+// the call came through kvc_observe_*_paged, which also takes fp8 keys (Q is then bf16) and, with
+// `pages`, K behind block tables; kvc_observe_plan / _score keep the rule set they had.
 static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* op,
-                             const kvc_layer_t* layers, const kvc_observe_layer_t* ol, int nl,
+                             const kvc_layer_t* layers, const kvc_observe_layer_t* ol,
+                             const kvc_pages_t* pages, bool sources, int nl,
                              kvc_plan_info_t* info, ObserveLayout* lay) {
   if (!p || !op || nl < 0 || (nl > 0 && (!layers || !ol))) return KVC_E_ARG;
   int rc = plan_impl(p, const_cast<kvc_layer_t*>(layers), nl, info, false);
   if (rc != KVC_OK) return rc;
-  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16) return KVC_E_DTYPE;
+  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16 && !(sources && is_fp8(p->dtype)))
+    return KVC_E_DTYPE;
+  const int es = esize(p->dtype);  // K's element; Q's is 2 bytes (bf16 beside fp8 keys)
   if (p->head_dim != 64 && p->head_dim != 128 && p->head_dim != 256) return KVC_E_HEADDIM;
   if (p->external_index) return KVC_E_ARG;
   const int W = op->window;
@@ -1131,10 +1137,15 @@ static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* 
     if (y.zone_len == 0) continue;
     if (y.seq_len < W + 1 || (int64_t)y.zone_start + y.zone_len > y.seq_len - W) return KVC_E_ARG;
     if (!y.k || !q.q) return KVC_E_ARG;
+    if (pages) {  // kvc_plan_paged's page rules; the entry only reads K: in_place is not read
+      kvc_pages_t g = pages[l];
+      g.in_place = 0;
+      if ((rc = paged_layer_check(p, y, g, false)) != KVC_OK) return rc;
+    }
     if (!aligned16(y.k) || !aligned16(q.q)) return KVC_E_ALIGN;
-    if ((p->batch > 1 && ((y.k_stride[0] * 2) % 16 || (q.q_stride[0] * 2) % 16)) ||
-        (p->heads > 1 && (y.k_stride[1] * 2) % 16) || (op->q_heads > 1 && (q.q_stride[1] * 2) % 16) ||
-        (y.k_stride[2] * 2) % 16 || (q.q_stride[2] * 2) % 16)
+    if ((p->batch > 1 && ((y.k_stride[0] * es) % 16 || (q.q_stride[0] * 2) % 16)) ||
+        (p->heads > 1 && (y.k_stride[1] * es) % 16) || (op->q_heads > 1 && (q.q_stride[1] * 2) % 16) ||
+        (y.k_stride[2] * es) % 16 || (q.q_stride[2] * 2) % 16)
       return KVC_E_ALIGN;
     lay->max_seq = y.seq_len > lay->max_seq ? y.seq_len : lay->max_seq;
     lay->max_zone = y.zone_len > lay->max_zone ? y.zone_len : lay->max_zone;
@@ -1162,13 +1173,33 @@ static int launch_observe_chunk(const ObserveChunk& C, const ObserveArgs& A, int
                   dim3(kPoolThreads), 0, s, C, A);
 }
 
+// The kernels of one chunk whose keys are paged and / or fp8: observe_src_kernel for the two
+// passes, and the dense call's pooling kernel (it reads the layer table and scratch only).
+template <int DT, int NC, bool PAGED>
+static int launch_observe_src_chunk(const ObserveChunk& C, const ObservePages& G,
+                                    const ObserveArgs& A, uint32_t* status, int cn, int max_seq,
+                                    int max_zone, hipStream_t s) {
+  const unsigned rows = (unsigned)(cn * A.BH);
+  const dim3 pass_grid(rows, (unsigned)((max_seq + kObsChunk - 1) / kObsChunk));
+  int rc = launch_k(observe_src_kernel<DT, NC, 1, false, PAGED>, pass_grid, dim3(kObsThreads), 0, s,
+                    C, G, A, status);
+  if (rc != KVC_OK) return rc;
+  rc = launch_k(observe_src_kernel<DT, NC, 2, kObsPass2NT, PAGED>, pass_grid, dim3(kObsThreads), 0,
+                s, C, G, A, status);
+  if (rc != KVC_OK) return rc;
+  return launch_k(observe_pool_kernel<score_dt(DT)>,
+                  dim3(rows, (unsigned)((max_zone + kPoolThreads - 1) / kPoolThreads)),
+                  dim3(kPoolThreads), 0, s, C, A);
+}
+
 static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t* op,
-                              const kvc_layer_t* layers, const kvc_observe_layer_t* ol, int nl,
-                              char* w, size_t wbytes, char* scratch, size_t sbytes, float* f32,
+                              const kvc_layer_t* layers, const kvc_observe_layer_t* ol,
+                              const kvc_pages_t* pages, bool sources, int nl, char* w,
+                              size_t wbytes, char* scratch, size_t sbytes, float* f32,
                               hipStream_t s) {
   kvc_plan_info_t info;
   ObserveLayout lay;
-  int rc = observe_plan_impl(p, op, layers, ol, nl, &info, &lay);
+  int rc = observe_plan_impl(p, op, layers, ol, pages, sources, nl, &info, &lay);
   if (rc != KVC_OK) return rc;
   if (nl == 0 || lay.max_zone == 0) return KVC_OK;
   if (!w || wbytes < info.workspace_bytes || !scratch || sbytes < lay.total) return KVC_E_WORKSPACE;
@@ -1185,7 +1216,7 @@ static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t*
   A.part = reinterpret_cast<float2*>(scratch);
   A.imp = reinterpret_cast<float*>(scratch + lay.part_bytes);
   A.norms = w + info.norm_offset, A.f32 = f32;
-  const int nc = p->head_dim * 2 / 16;
+  const int nc = p->head_dim * 2 / 16;  // 16-B chunks of an LDS row: bf16 / fp16 (fp8: widened)
   for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kObsLayers) {
     const int cn = nl - c0 < kObsLayers ? nl - c0 : kObsLayers;
     ObserveChunk C;
@@ -1207,8 +1238,43 @@ static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t*
         default: return launch_observe_chunk<DT, 32>(C, A, cn, max_seq, max_zone, s);
       }
     };
-    rc = p->dtype == KVC_BF16 ? go(std::integral_constant<int, KVC_BF16>())
-                              : go(std::integral_constant<int, KVC_F16>());
+    if (!pages && !is_fp8(p->dtype)) {  // dense 16-bit keys: the kernels of kvc_observe_score
+      rc = p->dtype == KVC_BF16 ? go(std::integral_constant<int, KVC_BF16>())
+                                : go(std::integral_constant<int, KVC_F16>());
+      continue;
+    }
+    ObservePages G;
+    memset(&G, 0, sizeof(G));
+    if (pages) memcpy(G.p, pages + c0, (size_t)cn * sizeof(kvc_pages_t));
+    const auto src = [&](auto dt, auto pg) {
+      constexpr int DT = decltype(dt)::value;
+      constexpr bool PAGED = decltype(pg)::value;
+      // (dense 16-bit keys took the branch above: no observe_src_kernel instance for them)
+      if constexpr (!PAGED && !is_fp8(DT)) {
+        return (int)KVC_E_ARG;
+      } else {
+        switch (nc) {
+          case 8:
+            return launch_observe_src_chunk<DT, 8, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                          max_zone, s);
+          case 16:
+            return launch_observe_src_chunk<DT, 16, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                           max_zone, s);
+          default:
+            return launch_observe_src_chunk<DT, 32, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                           max_zone, s);
+        }
+      }
+    };
+    const auto with_src = [&](auto dt) {
+      return pages ? src(dt, std::true_type()) : src(dt, std::false_type());
+    };
+    switch (p->dtype) {
+      case KVC_BF16: rc = with_src(std::integral_constant<int, KVC_BF16>()); break;
+      case KVC_F16: rc = with_src(std::integral_constant<int, KVC_F16>()); break;
+      case KVC_F8E4M3: rc = with_src(std::integral_constant<int, KVC_F8E4M3>()); break;
+      default: rc = with_src(std::integral_constant<int, KVC_F8E5M2>()); break;
+    }
   }
   return rc;
 }
@@ -1475,7 +1541,20 @@ int kvc_observe_plan(const kvc_params_t* params, const kvc_observe_params_t* opa
   kvc_plan_info_t info;
   kvc::ObserveLayout lay;
   if (!scratch_bytes) return KVC_E_ARG;
-  const int rc = kvc::observe_plan_impl(params, oparams, layers, olayers, num_layers, &info, &lay);
+  const int rc = kvc::observe_plan_impl(params, oparams, layers, olayers, nullptr, false,
+                                        num_layers, &info, &lay);
+  if (rc == KVC_OK) *scratch_bytes = lay.total;
+  return rc;
+}
+
+int kvc_observe_plan_paged(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                           const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                           const kvc_pages_t* pages, int num_layers, size_t* scratch_bytes) {
+  kvc_plan_info_t info;
+  kvc::ObserveLayout lay;
+  if (!scratch_bytes) return KVC_E_ARG;
+  const int rc = kvc::observe_plan_impl(params, oparams, layers, olayers, pages, true, num_layers,
+                                        &info, &lay);
   if (rc == KVC_OK) *scratch_bytes = lay.total;
   return rc;
 }
@@ -1484,7 +1563,18 @@ int kvc_observe_score(const kvc_params_t* params, const kvc_observe_params_t* op
                       const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
                       int num_layers, void* workspace, size_t workspace_bytes, void* scratch,
                       size_t scratch_bytes, float* scores_f32, kvc_stream_t stream) {
-  return kvc::observe_score_impl(params, oparams, layers, olayers, num_layers,
+  return kvc::observe_score_impl(params, oparams, layers, olayers, nullptr, false, num_layers,
+                                 static_cast<char*>(workspace), workspace_bytes,
+                                 static_cast<char*>(scratch), scratch_bytes, scores_f32,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+int kvc_observe_score_paged(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                            const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                            const kvc_pages_t* pages, int num_layers, void* workspace,
+                            size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                            float* scores_f32, kvc_stream_t stream) {
+  return kvc::observe_score_impl(params, oparams, layers, olayers, pages, true, num_layers,
                                  static_cast<char*>(workspace), workspace_bytes,
                                  static_cast<char*>(scratch), scratch_bytes, scores_f32,
                                  reinterpret_cast<hipStream_t>(stream));

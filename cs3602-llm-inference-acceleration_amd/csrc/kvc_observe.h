@@ -32,6 +32,10 @@
 // to 16 different granules of the 256-B bank line -- rows r and r + 16 first share one, and they
 // are in different phases -- the rule kvc_score.h's slab uses; checked the same way, by the
 // addresses: (r * (NC + 1) + c) mod 16 is a bijection of r in [0, 16) for even NC.
+//
+// Paged and fp8 keys (kvc_observe_score_paged) run the pass kernel of kvc_observe_src.h: a COPY of
+// observe_pass_kernel with another tile loader, kept apart so that the dense 16-bit instances stay
+// the code they were.  A fix to one pass body is a fix to both.
 #pragma once
 
 #include "kvc_device_util.h"

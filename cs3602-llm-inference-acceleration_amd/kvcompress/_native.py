@@ -138,7 +138,8 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_heavy_hitters", "kvc_debug_select_capacity", "kvc_plan_dest", "kvc_launch_dest",
            "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged",
            "kvc_plan_scaled", "kvc_launch_scaled", "kvc_plan_repage", "kvc_launch_repage",
-           "kvc_observe_plan", "kvc_observe_score")
+           "kvc_observe_plan", "kvc_observe_score", "kvc_observe_plan_paged",
+           "kvc_observe_score_paged")
 
 _lib = None
 
@@ -213,6 +214,15 @@ def lib():
         L.kvc_observe_score.restype = i32
         L.kvc_observe_score.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(ObserveParams), vp,
                                         vp, i32, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    if hasattr(L, "kvc_observe_plan_paged"):  # additive within ABI 4, like the observe entries
+        L.kvc_observe_plan_paged.restype = i32
+        L.kvc_observe_plan_paged.argtypes = [ctypes.POINTER(Params),
+                                             ctypes.POINTER(ObserveParams), vp, vp, vp, i32,
+                                             ctypes.POINTER(ctypes.c_size_t)]
+        L.kvc_observe_score_paged.restype = i32
+        L.kvc_observe_score_paged.argtypes = [ctypes.POINTER(Params),
+                                              ctypes.POINTER(ObserveParams), vp, vp, vp, i32, vp,
+                                              ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -428,6 +438,38 @@ def observe_score(params, oparams, table, otable, ws_ptr, ws_bytes, scratch_ptr,
     return lib().kvc_observe_score(ctypes.byref(params), ctypes.byref(oparams), table.ctypes.data,
                                    otable.ctypes.data, len(table), ws_ptr, ws_bytes, scratch_ptr,
                                    scratch_bytes, f32_ptr, stream_ptr)
+
+
+def _need_observe_paged_entries():
+    if not hasattr(lib(), "kvc_observe_plan_paged"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_observe_plan_paged / "
+                                 "kvc_observe_score_paged (built before paged and fp8 "
+                                 "observation-window scores); they need the current library")
+
+
+def observe_plan_paged(params, oparams, table, otable, pages):
+    """kvc_observe_plan_paged: (rc, scratch bytes).  `pages` is a PAGES_DTYPE array, one entry
+    per layer, or None (dense K; fp8 keys are accepted)."""
+    assert otable.dtype == OBSERVE_LAYER_DTYPE and len(otable) == len(table)
+    _need_observe_paged_entries()
+    n = ctypes.c_size_t()
+    rc = lib().kvc_observe_plan_paged(ctypes.byref(params), ctypes.byref(oparams),
+                                      table.ctypes.data, otable.ctypes.data,
+                                      _opt(pages, PAGES_DTYPE, len(table)), len(table),
+                                      ctypes.byref(n))
+    return rc, n.value
+
+
+def observe_score_paged(params, oparams, table, otable, pages, ws_ptr, ws_bytes, scratch_ptr,
+                        scratch_bytes, f32_ptr, stream_ptr):
+    """kvc_observe_score_paged (pages None: dense K, fp8 keys accepted)."""
+    assert otable.dtype == OBSERVE_LAYER_DTYPE and len(otable) == len(table)
+    _need_observe_paged_entries()
+    return lib().kvc_observe_score_paged(ctypes.byref(params), ctypes.byref(oparams),
+                                         table.ctypes.data, otable.ctypes.data,
+                                         _opt(pages, PAGES_DTYPE, len(table)), len(table), ws_ptr,
+                                         ws_bytes, scratch_ptr, scratch_bytes, f32_ptr,
+                                         stream_ptr)
 
 
 class Tables:

@@ -220,8 +220,8 @@ const char* kvc_status_string(int status);
 /* SHA-256 (hex) of the sources this library was compiled from (csrc/kvc.hip, then the headers it
  * includes -- kvc_common.h, kvc_serial.h, kvc_device_util.h, kvc_score.h, kvc_snapkv_keys.h,
  * kvc_select_chain.h, kvc_select.h, kvc_gather.h, kvc_attn.h, kvc_gather_dest.h,
- * kvc_paged.h, kvc_ragged.h, kvc_repage.h, kvc_observe.h -- then include/kvc.h, in that order), or
- * "unknown" for builds that do not set it --
+ * kvc_paged.h, kvc_ragged.h, kvc_repage.h, kvc_observe.h, kvc_observe_src.h -- then include/kvc.h,
+ * in that order), or "unknown" for builds that do not set it --
  * lets a caller (and tests/test_abi.py) check that a shipped binary matches its source tree. */
 const char* kvc_source_digest(void);
 
@@ -656,11 +656,33 @@ int kvc_launch_repage(const kvc_params_t* params, const kvc_layer_t* layers,
  * external_index 0 (KVC_E_ARG).  Every layer carries score_mode = KVC_SCORE_NORM (KVC_E_ARG).  A
  * layer with zone_len > 0 has seq_len >= window + 1 and zone_start + zone_len <= seq_len - window
  * (KVC_E_ARG), k and q non-NULL (KVC_E_ARG) and 16-byte aligned, the strides of K's and Q's dims
- * larger than 1 multiples of 16 bytes, last dims contiguous (KVC_E_ALIGN).  K / V are dense
- * (kvc_layer_t's strides): there is no entry with page, ragged or scale tables.
+ * larger than 1 multiples of 16 bytes, last dims contiguous (KVC_E_ALIGN).  For kvc_observe_plan /
+ * kvc_observe_score K is dense (kvc_layer_t's strides) and 16-bit: that pair keeps exactly this rule
+ * set, fp8 -> KVC_E_DTYPE included.  Paged and fp8 keys go through the _paged pair below; there is
+ * no entry with ragged or scale tables.
  *
  * Launch discipline: three kernels per chunk of 32 layers (statistics, column sums, pooling),
  * every table by value in the kernel arguments; no allocation, synchronisation or global state.
+ *
+ * Paged and fp8 keys (kvc_observe_plan_paged / kvc_observe_score_paged; additive within ABI 4: a
+ * library without the two entries does not export them).  The rules, status codes, scratch layout
+ * and results above hold, with two extensions:
+ *   pages != NULL: every layer's K lives in a page pool behind a block table, pages[i] belongs to
+ *     layers[i], under the rules of "Paged caches" (kvc_plan_paged's checks: k_stride[0] and
+ *     v_stride[0] are 0, page_size a power of two in [1, 65536], table_stride >= ceil(seq_len /
+ *     page_size), block_table non-NULL and 4-byte aligned, num_pages >= 1, reserved 0 -- KVC_E_ARG;
+ *     the page stride a multiple of 16 bytes when num_pages > 1 -- KVC_E_ALIGN), applied to every
+ *     layer with zone_len > 0.  in_place is not read: the entry only reads K.  No table entry at or
+ *     past ceil(seq_len / page_size) is read.  A page id outside [0, num_pages) is clamped and
+ *     KVC_DEV_INDEX_RANGE is ORed into params.device_status; rows of (b, h) whose pages are in range
+ *     are not affected.  pages == NULL: dense K under kvc_layer_t's strides.
+ *   dtype may also be KVC_F8E4M3 or KVC_F8E5M2 (dense or paged): K is fp8, Q is BF16, the strides
+ *     and alignment rules of K count bytes of its 1-byte elements, and the norm region's dtype is
+ *     bf16, as on every fp8 path.  fp32 stays KVC_E_DTYPE.
+ * The scores of a paged or fp8 call are BIT FOR BIT those of the dense bf16 / fp16 call on the
+ * tensor the table describes (fp8: on K.to(bfloat16), an exact upcast): the kernels differ from the
+ * dense ones only in how a key tile reaches LDS.  Chunks stay 32 layers: layer, query and page
+ * tables are 7.2 KiB of kernel arguments, below the 7.5 KiB the paged launches run with.
  * ------------------------------------------------------------------------------------------- */
 enum kvc_observe_pool { KVC_OBS_POOL_AVG = 0, KVC_OBS_POOL_MAX = 1 };
 
@@ -696,6 +718,20 @@ int kvc_observe_score(const kvc_params_t* params, const kvc_observe_params_t* op
                       const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
                       int num_layers, void* workspace, size_t workspace_bytes, void* scratch,
                       size_t scratch_bytes, float* scores_f32, kvc_stream_t stream);
+
+/* kvc_observe_plan for paged and / or fp8 keys (see "Paged and fp8 keys" above).  With pages ==
+ * NULL and a 16-bit dtype it accepts what kvc_observe_plan accepts and reports the same bytes. */
+int kvc_observe_plan_paged(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                           const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                           const kvc_pages_t* pages, int num_layers, size_t* scratch_bytes);
+
+/* kvc_observe_score for paged and / or fp8 keys.  Re-validates as kvc_observe_plan_paged does; the
+ * kernels receive the page tables by value beside the layer and query tables. */
+int kvc_observe_score_paged(const kvc_params_t* params, const kvc_observe_params_t* oparams,
+                            const kvc_layer_t* layers, const kvc_observe_layer_t* olayers,
+                            const kvc_pages_t* pages, int num_layers, void* workspace,
+                            size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                            float* scores_f32, kvc_stream_t stream);
 
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |

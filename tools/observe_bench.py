@@ -11,9 +11,18 @@ over `--rounds` rounds, per geometry:
 `read_rate_vs_score` = score_ms / (observe_ms / 2): the rate at which each of the two passes
 reads K, as a fraction of SCORE's; above 1 the second pass was served from cache.
 KVC_LIB=<variant libkvc.so> measures a variant build (e.g. non-temporal pass-2 loads).
+
+--sources: what a block table and fp8 keys cost the same kernels (kvc_observe_score_paged).  Per
+geometry and source -- paged bf16 pools stored [N, P, H, D] behind shuffled tables at P = 16 and
+P = 128, and dense e4m3 keys -- one line with the source's observe set and whole call
+(snapkv_compress_paged / snapkv_compress) next to the dense bf16 set and call of the same build,
+alternating in one process: medians and ranges over `--rounds` rounds, and the ratios.  A paged
+call compacts in place, so from its second run on it ranks the rows its first run left: the
+kernels' work does not depend on the data.
 GPU box only.
 
   python tools/observe_bench.py [--layers 32] [--seq 16384] [--rounds 5] [--reps 10] [--out FILE]
+                                [--sources]
 """
 import argparse
 import json
@@ -29,7 +38,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cs3602-llm-inference-acceleration_amd"))
 from kvcompress import _engine as E  # noqa: E402
 from kvcompress import _native as N  # noqa: E402
-from kvcompress import snapkv_compress  # noqa: E402
+from kvcompress import PagedKV, snapkv_compress, snapkv_compress_paged  # noqa: E402
+from kvcompress.methods.snapkv import _paged_table  # noqa: E402
 
 DEV = torch.device("cuda:0")
 D, W, KEEP, POOL = 128, 32, 512, 5
@@ -108,6 +118,93 @@ def geometry(name, L, S, Hkv, G, rounds, reps, gen):
     return rec
 
 
+def observe_set(dtype, Hkv, G, table, qs, tables=None):
+    """The planned observe launch set of a table as a callable (kvc_observe_score_paged)."""
+    p = E._params(dtype, 1, Hkv, D, N.KVC_DESC, N.KVC_ALGO_TOPK, False)
+    ws, info = E._upload(p, table, 0, None, 1, Hkv, tables)
+    otable = np.zeros(len(table), dtype=N.OBSERVE_LAYER_DTYPE)
+    for i, q in enumerate(qs):
+        otable[i] = (q.data_ptr(), q.stride()[:3], 0)
+    op = N.ObserveParams(q_heads=G * Hkv, window=W, pool_kernel=POOL, pool_mode=N.OBS_POOL_AVG)
+    pages = tables.pages if tables is not None else None
+    rc, sbytes = N.observe_plan_paged(p, op, table, otable, pages)
+    N.check(rc, "kvc_observe_plan_paged")
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    keep = (ws, scratch, otable, op, p, table, tables)
+
+    def run():
+        N.check(N.observe_score_paged(p, op, table, otable, pages, ws.data_ptr(),
+                                      int(info.workspace_bytes), scratch.data_ptr(), sbytes, None,
+                                      stream), "kvc_observe_score_paged")
+    run.keep = keep
+    return run
+
+
+def paged_layers(kv, P, gen):
+    """The layers' K / V in pools stored [N, P, H, D] behind a shuffled one-row table."""
+    out = []
+    for k, v in kv:
+        _, H, S, _ = k.shape
+        n = S // P
+        perm = torch.randperm(n + 7, device=DEV, generator=gen)[:n]
+        pools = []
+        for x in (k, v):
+            pool = torch.empty(n + 7, P, H, D, dtype=x.dtype, device=DEV)
+            pool[perm] = x[0].permute(1, 0, 2).reshape(n, P, H, D)
+            pools.append(pool.permute(0, 2, 1, 3))
+        out.append(PagedKV(pools[0], pools[1], perm.int().view(1, n), S))
+    return out
+
+
+def sources(name, L, S, Hkv, G, rounds, reps, gen):
+    kv = [tuple(torch.empty(1, Hkv, S, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+                for _ in range(2)) for _ in range(L)]
+    qs = [torch.empty(1, G * Hkv, W, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+          for _ in range(L)]
+    seg = (0, S - W, KEEP - W, 0, S - W, W)
+
+    def dense_runs(layers):
+        jobs = [E.Segments(i, k, v, zone_len=S - W, n_select=KEEP - W, tail_start=S - W,
+                           tail_len=W) for i, (k, v) in enumerate(layers)]
+        table = E._build_table(0, layers[0][0].dtype, 1, Hkv, D, jobs)
+        run = observe_set(layers[0][0].dtype, Hkv, G, table[0], qs)
+        run.keep += (table,)
+        return run, lambda: snapkv_compress(layers, qs, W, KEEP, POOL)
+
+    base_obs, base_call = dense_runs(kv)
+    lines = []
+    for src in ("paged_p16", "paged_p128", "fp8_e4m3"):
+        if src.startswith("paged"):
+            pks = paged_layers(kv, int(src[7:]), gen)
+            table, tables = _paged_table(pks, [seg] * L)
+            obs = observe_set(torch.bfloat16, Hkv, G, table, qs, tables)
+            call = lambda: snapkv_compress_paged(pks, qs, W, KEEP, POOL)  # noqa: E731
+        else:
+            kv8 = [(k.to(torch.float8_e4m3fn), v.to(torch.float8_e4m3fn)) for k, v in kv]
+            obs, call = dense_runs(kv8)
+        runs = {"dense_observe_ms": base_obs, "observe_ms": obs, "dense_call_ms": base_call,
+                "call_ms": call}
+        for fn in runs.values():
+            fn()
+        torch.cuda.synchronize()
+        times = {key: [] for key in runs}
+        for _ in range(rounds):  # alternating
+            for key, fn in runs.items():
+                times[key].append(timed(fn, reps))
+        rec = {"geometry": name, "source": src, "layers": L, "seq": S, "kv_heads": Hkv, "group": G,
+               "window": W, "rounds": rounds, "lib": os.path.basename(N.LIB_PATH)}
+        for key, v in times.items():
+            rec[key] = round(statistics.median(v), 4)
+            rec[key + "_min_max"] = [round(min(v), 4), round(max(v), 4)]
+        rec["observe_vs_dense"] = round(rec["observe_ms"] / rec["dense_observe_ms"], 3)
+        rec["call_vs_dense"] = round(rec["call_ms"] / rec["dense_call_ms"], 3)
+        lines.append(json.dumps(rec))
+        del obs, call, runs
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
@@ -115,12 +212,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out")
+    ap.add_argument("--sources", action="store_true",
+                    help="paged (P = 16, 128) and fp8 keys next to the dense bf16 set")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("observe_bench needs the GPU")
     gen = torch.Generator(device=DEV).manual_seed(0)
-    lines = [json.dumps(geometry(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen))
-             for n, h, g in (("mha_h32", 32, 1), ("gqa_h8_g4", 8, 4))]
+    geos = (("mha_h32", 32, 1), ("gqa_h8_g4", 8, 4))
+    if a.sources:
+        lines = [ln for n, h, g in geos
+                 for ln in sources(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen)]
+    else:
+        lines = [json.dumps(geometry(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen))
+                 for n, h, g in geos]
     print("\n".join(lines))
     if a.out:
         with open(a.out, "a") as f:
