@@ -44,6 +44,7 @@
 #include "kvc_repage.h"         // GATHER through a destination block table (kvc_launch_repage)
 #include "kvc_observe.h"        // observation-window scores on the MFMA units (kvc_observe_score)
 #include "kvc_observe_src.h"    // ... of paged and fp8 keys (kvc_observe_score_paged)
+#include "kvc_observe_wide.h"   // ... of wide query groups: any G <= 16, G * W <= 256
 
 namespace kvc {
 
@@ -1100,15 +1101,18 @@ static int debug_select_impl(const kvc_params_t* p, const kvc_layer_t* layers, i
 
 // ---- observation-window scores (kvc_observe.h) ----------------------------------------------
 // Scratch of kvc_observe_score: the statistics partials [rows][pstride][32] float2, then the
-// column sums [rows][istride] fp32; strides by the longest scored layer and zone.
+// column sums [rows][istride] fp32; strides by the longest scored layer and zone.  wide: the call
+// runs the kernels of kvc_observe_wide.h (kObsWideBlocks partial slots per chunk, not kObsWaves).
 struct ObserveLayout {
   int64_t pstride, istride, max_seq, max_zone;
   size_t part_bytes, total;
+  bool wide;
 };
 
 // include/kvc.h, "Observation-window scores": the rules of a call on a planned table.  sources:
 // the call came through kvc_observe_*_paged, which also takes fp8 keys (Q is then bf16) and, with
-// `pages`, K behind block tables; kvc_observe_plan / _score keep the rule set they had.
+// `pages`, K behind block tables, and any group size G <= 16 with G * W <= kObsWideMaxM;
+// kvc_observe_plan / _score keep the rule set they had.
 static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* op,
                              const kvc_layer_t* layers, const kvc_observe_layer_t* ol,
                              const kvc_pages_t* pages, bool sources, int nl,
@@ -1125,7 +1129,9 @@ static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* 
   if (W != 16 && W != 32 && W != 64) return KVC_E_ARG;
   if (op->q_heads < p->heads || op->q_heads % p->heads) return KVC_E_ARG;
   const int G = op->q_heads / p->heads;
-  if ((G != 1 && G != 2 && G != 4 && G != 8) || G * W > kObsMaxM) return KVC_E_ARG;
+  lay->wide = observe_wide(G, (G * W + 31) / 32);
+  if (sources ? (G > 16 || G * W > kObsWideMaxM) : (lay->wide || G * W > kObsMaxM))
+    return KVC_E_ARG;
   if (op->pool_kernel < 1 || op->pool_kernel > 7 || !(op->pool_kernel & 1)) return KVC_E_ARG;
   if (op->pool_mode != KVC_OBS_POOL_AVG && op->pool_mode != KVC_OBS_POOL_MAX) return KVC_E_ARG;
   if (op->reserved != 0 || !(op->scale - op->scale == 0.f)) return KVC_E_ARG;  // finite
@@ -1150,7 +1156,8 @@ static int observe_plan_impl(const kvc_params_t* p, const kvc_observe_params_t* 
     lay->max_seq = y.seq_len > lay->max_seq ? y.seq_len : lay->max_seq;
     lay->max_zone = y.zone_len > lay->max_zone ? y.zone_len : lay->max_zone;
   }
-  lay->pstride = (lay->max_seq + kObsChunk - 1) / kObsChunk * kObsWaves;
+  lay->pstride = (lay->max_seq + kObsChunk - 1) / kObsChunk *
+                 (lay->wide ? kObsWideBlocks : kObsWaves);
   lay->istride = (int64_t)round_up((size_t)lay->max_zone, kTile);
   lay->part_bytes = round_up((size_t)info->rows * lay->pstride * 32 * sizeof(float2), 256);
   lay->total = lay->part_bytes + (size_t)info->rows * lay->istride * sizeof(float);
@@ -1186,6 +1193,25 @@ static int launch_observe_src_chunk(const ObserveChunk& C, const ObservePages& G
   if (rc != KVC_OK) return rc;
   rc = launch_k(observe_src_kernel<DT, NC, 2, kObsPass2NT, PAGED>, pass_grid, dim3(kObsThreads), 0,
                 s, C, G, A, status);
+  if (rc != KVC_OK) return rc;
+  return launch_k(observe_pool_kernel<score_dt(DT)>,
+                  dim3(rows, (unsigned)((max_zone + kPoolThreads - 1) / kPoolThreads)),
+                  dim3(kPoolThreads), 0, s, C, A);
+}
+
+// The kernels of one chunk of a wide query group (kvc_observe_wide.h), whatever the key source;
+// pooling is the shared kernel.
+template <int DT, int NC, bool PAGED>
+static int launch_observe_wide_chunk(const ObserveChunk& C, const ObservePages& G,
+                                     const ObserveArgs& A, uint32_t* status, int cn, int max_seq,
+                                     int max_zone, hipStream_t s) {
+  const unsigned rows = (unsigned)(cn * A.BH);
+  const dim3 pass_grid(rows, (unsigned)((max_seq + kObsChunk - 1) / kObsChunk));
+  int rc = launch_k(observe_wide_kernel<DT, NC, 1, false, PAGED>, pass_grid, dim3(kObsThreads), 0,
+                    s, C, G, A, status);
+  if (rc != KVC_OK) return rc;
+  rc = launch_k(observe_wide_kernel<DT, NC, 2, kObsPass2NT, PAGED>, pass_grid, dim3(kObsThreads),
+                0, s, C, G, A, status);
   if (rc != KVC_OK) return rc;
   return launch_k(observe_pool_kernel<score_dt(DT)>,
                   dim3(rows, (unsigned)((max_zone + kPoolThreads - 1) / kPoolThreads)),
@@ -1238,7 +1264,8 @@ static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t*
         default: return launch_observe_chunk<DT, 32>(C, A, cn, max_seq, max_zone, s);
       }
     };
-    if (!pages && !is_fp8(p->dtype)) {  // dense 16-bit keys: the kernels of kvc_observe_score
+    // dense 16-bit keys of a group the 4-block schedule serves: the kernels of kvc_observe_score
+    if (!lay.wide && !pages && !is_fp8(p->dtype)) {
       rc = p->dtype == KVC_BF16 ? go(std::integral_constant<int, KVC_BF16>())
                                 : go(std::integral_constant<int, KVC_F16>());
       continue;
@@ -1249,6 +1276,19 @@ static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t*
     const auto src = [&](auto dt, auto pg) {
       constexpr int DT = decltype(dt)::value;
       constexpr bool PAGED = decltype(pg)::value;
+      if (lay.wide) {  // G not a power of two, or more than four query blocks
+        switch (nc) {
+          case 8:
+            return launch_observe_wide_chunk<DT, 8, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                           max_zone, s);
+          case 16:
+            return launch_observe_wide_chunk<DT, 16, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                            max_zone, s);
+          default:
+            return launch_observe_wide_chunk<DT, 32, PAGED>(C, G, A, p->device_status, cn, max_seq,
+                                                            max_zone, s);
+        }
+      }
       // (dense 16-bit keys took the branch above: no observe_src_kernel instance for them)
       if constexpr (!PAGED && !is_fp8(DT)) {
         return (int)KVC_E_ARG;

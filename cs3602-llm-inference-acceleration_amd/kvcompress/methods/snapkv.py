@@ -93,9 +93,16 @@ class _Group:
             fstride = (int(table["zone_len"].max()) + 63) // 64 * 64
             self.op = N.ObserveParams(q_heads=Hq, window=W, scale=scale or 0.0, pool_kernel=pool,
                                       pool_mode=mode, scores_row_stride=fstride)
-            # dense 16-bit keys keep their entry pair; pages and fp8 keys take the _paged pair
+            G = Hq // H
+            if G > 16 or G * W > 256:
+                raise ValueError(f"kvcompress: observation-window scores take query groups of "
+                                 f"G <= 16 heads per KV head with G * window <= 256; got G = {G} "
+                                 f"(Hq = {Hq}, Hkv = {H}) at window {W}")
+            # dense 16-bit keys keep their entry pair where it admits the group (G a power of two,
+            # G * W <= 128); pages, fp8 keys and every other group take the _paged pair
             self.pages = tables.pages if tables is not None else None
-            self.paged_entry = self.pages is not None or E.is_fp8(dtype)
+            self.paged_entry = self.pages is not None or E.is_fp8(dtype) or \
+                G not in (1, 2, 4, 8) or G * W > 128
             if self.paged_entry:
                 rc, self.sbytes = N.observe_plan_paged(p, self.op, table, self.otable, self.pages)
                 N.check(rc, "kvc_observe_plan_paged")

@@ -683,6 +683,16 @@ int kvc_launch_repage(const kvc_params_t* params, const kvc_layer_t* layers,
  * tensor the table describes (fp8: on K.to(bfloat16), an exact upcast): the kernels differ from the
  * dense ones only in how a key tile reaches LDS.  Chunks stay 32 layers: layer, query and page
  * tables are 7.2 KiB of kernel arguments, below the 7.5 KiB the paged launches run with.
+ *
+ * Wide query groups (the _paged pair only; additive within ABI 4).  kvc_observe_plan_paged /
+ * kvc_observe_score_paged take q_heads = G * heads with G ANY integer in [1, 16] and G * window
+ * <= 256, for every key source above (dense with pages == NULL, paged, fp8).  Everything else is
+ * unchanged: G > 16, G * window > 256 and a window other than 16, 32 or 64 are KVC_E_ARG.
+ * kvc_observe_plan / kvc_observe_score keep G in {1, 2, 4, 8} and G * window <= 128.  For a shape
+ * both pairs accept the _paged pair reports the same scratch bytes and runs the same kernels; the
+ * other groups run a wider schedule (up to eight blocks of 32 query rows per workgroup) with its
+ * own, larger statistics scratch.  The arithmetic, the determinism and the bit-for-bit equality
+ * of paged and fp8 calls with the dense call of the same group hold as above.
  * ------------------------------------------------------------------------------------------- */
 enum kvc_observe_pool { KVC_OBS_POOL_AVG = 0, KVC_OBS_POOL_MAX = 1 };
 

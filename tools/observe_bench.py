@@ -19,10 +19,15 @@ P = 128, and dense e4m3 keys -- one line with the source's observe set and whole
 alternating in one process: medians and ranges over `--rounds` rounds, and the ratios.  A paged
 call compacts in place, so from its second run on it ranks the rows its first run left: the
 kernels' work does not depend on the data.
+
+--wide: wide query groups (csrc/kvc_observe_wide.h).  32 layers of [1, 8, 16384, 128] bf16 at
+W = 32 with G = 8 (Hq = 64) and, the uneven point, G = 7 (Hq = 56): the observe set and the whole
+snapkv_compress call next to the query heads split into admitted groups (observation_scores at
+pooling_kernel = 1 per group, added and pooled in torch) and the torch line, alternating.
 GPU box only.
 
   python tools/observe_bench.py [--layers 32] [--seq 16384] [--rounds 5] [--reps 10] [--out FILE]
-                                [--sources]
+                                [--sources | --wide]
 """
 import argparse
 import json
@@ -38,7 +43,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cs3602-llm-inference-acceleration_amd"))
 from kvcompress import _engine as E  # noqa: E402
 from kvcompress import _native as N  # noqa: E402
-from kvcompress import PagedKV, snapkv_compress, snapkv_compress_paged  # noqa: E402
+from kvcompress import PagedKV, observation_scores, snapkv_compress, snapkv_compress_paged  # noqa: E402,E501
 from kvcompress.methods.snapkv import _paged_table  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -205,6 +210,57 @@ def sources(name, L, S, Hkv, G, rounds, reps, gen):
     return lines
 
 
+def wide(name, L, S, Hkv, G, rounds, reps, gen):
+    """A wide query group (kvc_observe_wide.h): the observe set and the whole snapkv_compress call
+    beside the two ways round it: the query heads split into observation_scores calls of groups
+    the 4-block schedule admits at pooling_kernel = 1 (G = 8: two G = 4 calls; G = 7: G = 4, 2 and
+    1), added and pooled in torch; and the torch line."""
+    kv = [tuple(torch.empty(1, Hkv, S, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+                for _ in range(2)) for _ in range(L)]
+    qs = [torch.empty(1, G * Hkv, W, D, dtype=torch.bfloat16, device=DEV).normal_(generator=gen)
+          for _ in range(L)]
+    ks = [k for k, _ in kv]
+    jobs = [E.Segments(i, k, v, zone_len=S - W, n_select=KEEP - W, tail_start=S - W, tail_len=W)
+            for i, (k, v) in enumerate(kv)]
+    table = E._build_table(0, torch.bfloat16, 1, Hkv, D, jobs)
+    obs = observe_set(torch.bfloat16, Hkv, G, table[0], qs)
+    # the admitted groups the heads split into, as slices of a KV head's G query heads
+    parts, g0 = [], 0
+    for g in (4, 2, 1):
+        while G - g0 >= g:
+            parts.append((g0, g))
+            g0 += g
+    qparts = [[q.view(1, Hkv, G, W, D)[:, :, a:a + g].reshape(1, Hkv * g, W, D).contiguous()
+               for q in qs] for a, g in parts]
+
+    def split():
+        out = None
+        for qp in qparts:
+            imp = torch.stack(observation_scores(ks, qp, pooling_kernel=1))
+            out = imp if out is None else out + imp
+        return F.avg_pool1d(out.flatten(0, 2)[None], POOL, 1, POOL // 2)
+
+    runs = {"observe_ms": obs, "split_ms": split,
+            "call_ms": lambda: snapkv_compress(kv, qs, W, KEEP, POOL),
+            "torch_ms": lambda: torch_scores(kv, qs, G)}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {key: [] for key in runs}
+    for _ in range(rounds):  # alternating
+        for key, fn in runs.items():
+            times[key].append(timed(fn, reps if key != "torch_ms" else 2))
+    rec = {"geometry": name, "layers": L, "seq": S, "kv_heads": Hkv, "group": G, "window": W,
+           "split_groups": [g for _, g in parts], "k_bytes": L * Hkv * S * D * 2,
+           "rounds": rounds, "lib": os.path.basename(N.LIB_PATH)}
+    for key, v in times.items():
+        rec[key] = round(statistics.median(v), 4)
+        rec[key + "_min_max"] = [round(min(v), 4), round(max(v), 4)]
+    rec["observe_vs_split"] = round(rec["observe_ms"] / rec["split_ms"], 3)
+    rec["observe_gbps_two_reads"] = round(2 * rec["k_bytes"] / rec["observe_ms"] / 1e6, 1)
+    return json.dumps(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
@@ -214,12 +270,17 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--sources", action="store_true",
                     help="paged (P = 16, 128) and fp8 keys next to the dense bf16 set")
+    ap.add_argument("--wide", action="store_true",
+                    help="wide query groups (G = 8 and G = 7 at W = 32) next to the split calls")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("observe_bench needs the GPU")
     gen = torch.Generator(device=DEV).manual_seed(0)
     geos = (("mha_h32", 32, 1), ("gqa_h8_g4", 8, 4))
-    if a.sources:
+    if a.wide:
+        lines = [wide(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen)
+                 for n, h, g in (("gqa_h8_g8", 8, 8), ("gqa_h8_g7", 8, 7))]
+    elif a.sources:
         lines = [ln for n, h, g in geos
                  for ln in sources(n, a.layers, a.seq, h, g, a.rounds, a.reps, gen)]
     else:
