@@ -45,6 +45,7 @@
 #include "kvc_observe.h"        // observation-window scores on the MFMA units (kvc_observe_score)
 #include "kvc_observe_src.h"    // ... of paged and fp8 keys (kvc_observe_score_paged)
 #include "kvc_observe_wide.h"   // ... of wide query groups: any G <= 16, G * W <= 256
+#include "kvc_colsum.h"         // causal attention column sums on the MFMA units (kvc_colsum_score)
 
 namespace kvc {
 
@@ -1319,6 +1320,121 @@ static int observe_score_impl(const kvc_params_t* p, const kvc_observe_params_t*
   return rc;
 }
 
+// ---- causal attention column sums (kvc_colsum.h) ----------------------------------------------
+// One layer's split and its place in the scratch: the lse rows of all layers without a caller's
+// lse come first (`lse` bytes so far), then their partials (`part` bytes so far).
+static void colsum_layer_scratch(int64_t R, const kvc_colsum_layer_t& y, ColsumSplit* s,
+                                 size_t* lse, size_t* part) {
+  memset(s, 0, sizeof(*s));
+  if (y.lse) return;
+  colsum_split(R, y.q_len, y.seq_len, s);
+  s->lse_off = (int64_t)(*lse / sizeof(float));
+  s->part_off = (int64_t)(*part / sizeof(float2));
+  *lse += round_up((size_t)R * y.q_len * sizeof(float), 256);
+  *part += (size_t)R * s->nqb * s->nsplit * kObsWaves * 32 * sizeof(float2);
+}
+
+// include/kvc.h, "Causal attention column sums": the rules of a call and its scratch bytes.
+static int colsum_plan_impl(const kvc_colsum_params_t* p, const kvc_colsum_layer_t* layers, int nl,
+                            size_t* lse_bytes, size_t* total) {
+  if (!p || nl < 0 || (nl > 0 && !layers)) return KVC_E_ARG;
+  if (p->dtype != KVC_BF16 && p->dtype != KVC_F16) return KVC_E_DTYPE;
+  if (p->head_dim != 64 && p->head_dim != 80 && p->head_dim != 128 && p->head_dim != 256)
+    return KVC_E_HEADDIM;
+  if (p->batch < 1 || p->heads < 1 || p->q_heads < p->heads || p->q_heads % p->heads ||
+      p->q_heads / p->heads > 16)
+    return KVC_E_ARG;
+  if (p->reserved[0] != 0 || p->reserved[1] != 0 || !(p->scale - p->scale == 0.f)) return KVC_E_ARG;
+  const int64_t R = (int64_t)p->batch * p->q_heads;
+  if (R * (nl < kColsumLayers ? nl : kColsumLayers) > 0x7FFFFFFF) return KVC_E_ARG;
+  size_t lse = 0, part = 0;
+  for (int l = 0; l < nl; ++l) {
+    const kvc_colsum_layer_t& y = layers[l];
+    if (y.reserved != 0 || y.q_len < 1 || y.q_len > y.seq_len || y.seq_len > (1 << 20) ||
+        y.out_stride < y.seq_len || !y.k || !y.q || (!y.out_f32 && !y.out_dt))
+      return KVC_E_ARG;
+    if (!aligned16(y.k) || !aligned16(y.q) || ((uintptr_t)y.lse & 3u) ||
+        ((uintptr_t)y.out_f32 & 3u) || ((uintptr_t)y.out_dt & 1u))
+      return KVC_E_ALIGN;
+    if ((p->batch > 1 && ((y.k_stride[0] * 2) % 16 || (y.q_stride[0] * 2) % 16)) ||
+        (p->heads > 1 && (y.k_stride[1] * 2) % 16) || (p->q_heads > 1 && (y.q_stride[1] * 2) % 16) ||
+        (y.k_stride[2] * 2) % 16 || (y.q_stride[2] * 2) % 16)
+      return KVC_E_ALIGN;
+    ColsumSplit s;
+    colsum_layer_scratch(R, y, &s, &lse, &part);
+  }
+  *lse_bytes = lse, *total = lse + part;
+  return KVC_OK;
+}
+
+template <int DT, int NC>
+static int launch_colsum_chunk(const ColsumChunk& C, const ColsumArgs& A, int cn, bool stats,
+                               int max_nqb, int max_nsplit, int max_q, int max_seq, hipStream_t s) {
+  const unsigned qrows = (unsigned)(cn * A.B * A.Hq);
+  int rc = KVC_OK;
+  if (stats) {
+    rc = launch_k(colsum_stats_kernel<DT, NC>, dim3(qrows, (unsigned)max_nqb, (unsigned)max_nsplit),
+                  dim3(kObsThreads), 0, s, C, A);
+    if (rc != KVC_OK) return rc;
+    rc = launch_k(colsum_lse_kernel, dim3(qrows, (unsigned)((max_q + kLseThreads - 1) / kLseThreads)),
+                  dim3(kLseThreads), 0, s, C, A);
+    if (rc != KVC_OK) return rc;
+  }
+  return launch_k(colsum_sum_kernel<DT, NC>,
+                  dim3((unsigned)(cn * A.B * A.H), (unsigned)((max_seq + kObsTile - 1) / kObsTile)),
+                  dim3(kObsThreads), 0, s, C, A);
+}
+
+static int colsum_score_impl(const kvc_colsum_params_t* p, const kvc_colsum_layer_t* layers, int nl,
+                             char* scratch, size_t sbytes, hipStream_t s) {
+  size_t lse_bytes, total;
+  int rc = colsum_plan_impl(p, layers, nl, &lse_bytes, &total);
+  if (rc != KVC_OK) return rc;
+  if (nl == 0) return KVC_OK;
+  if (total > 0 && (!scratch || sbytes < total)) return KVC_E_WORKSPACE;
+  if (total > 0 && !aligned16(scratch)) return KVC_E_ALIGN;
+  ColsumArgs A;
+  A.B = p->batch, A.H = p->heads, A.Hq = p->q_heads, A.G = p->q_heads / p->heads;
+  const float scale = p->scale != 0.f ? p->scale : 1.f / __builtin_sqrtf((float)p->head_dim);
+  A.scale2 = scale * 1.44269504088896340736f;
+  A.lse = reinterpret_cast<float*>(scratch);
+  A.part = reinterpret_cast<float2*>(scratch + lse_bytes);
+  // the offsets of every layer's scratch run over the whole call, not the chunk
+  size_t lse = 0, part = 0;
+  const int64_t R = (int64_t)p->batch * p->q_heads;
+  for (int c0 = 0; c0 < nl && rc == KVC_OK; c0 += kColsumLayers) {
+    const int cn = nl - c0 < kColsumLayers ? nl - c0 : kColsumLayers;
+    ColsumChunk C;
+    memset(&C, 0, sizeof(C));
+    memcpy(C.l, layers + c0, (size_t)cn * sizeof(kvc_colsum_layer_t));
+    bool stats = false;
+    int max_nqb = 1, max_nsplit = 1, max_q = 1, max_seq = 1;
+    for (int l = 0; l < cn; ++l) {
+      const kvc_colsum_layer_t& y = C.l[l];
+      max_seq = y.seq_len > max_seq ? y.seq_len : max_seq;
+      ColsumSplit& sp = C.s[l];
+      colsum_layer_scratch(R, y, &sp, &lse, &part);
+      if (y.lse) continue;
+      stats = true;
+      max_nqb = sp.nqb > max_nqb ? sp.nqb : max_nqb;
+      max_nsplit = sp.nsplit > max_nsplit ? sp.nsplit : max_nsplit;
+      max_q = y.q_len > max_q ? y.q_len : max_q;
+    }
+    const auto go = [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      switch (p->head_dim) {
+        case 64: return launch_colsum_chunk<DT, 8>(C, A, cn, stats, max_nqb, max_nsplit, max_q, max_seq, s);
+        case 80: return launch_colsum_chunk<DT, 10>(C, A, cn, stats, max_nqb, max_nsplit, max_q, max_seq, s);
+        case 128: return launch_colsum_chunk<DT, 16>(C, A, cn, stats, max_nqb, max_nsplit, max_q, max_seq, s);
+        default: return launch_colsum_chunk<DT, 32>(C, A, cn, stats, max_nqb, max_nsplit, max_q, max_seq, s);
+      }
+    };
+    rc = p->dtype == KVC_BF16 ? go(std::integral_constant<int, KVC_BF16>())
+                              : go(std::integral_constant<int, KVC_F16>());
+  }
+  return rc;
+}
+
 // ---- h2o_attention host side ----------------------------------------------------------------
 static int attn_params_check(const kvc_attn_params_t* p, bool accumulate = false) {
   if (!p) return KVC_E_ARG;
@@ -1618,6 +1734,21 @@ int kvc_observe_score_paged(const kvc_params_t* params, const kvc_observe_params
                                  static_cast<char*>(workspace), workspace_bytes,
                                  static_cast<char*>(scratch), scratch_bytes, scores_f32,
                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int kvc_colsum_plan(const kvc_colsum_params_t* params, const kvc_colsum_layer_t* layers,
+                    int num_layers, size_t* scratch_bytes) {
+  size_t lse_bytes, total;
+  if (!scratch_bytes) return KVC_E_ARG;
+  const int rc = kvc::colsum_plan_impl(params, layers, num_layers, &lse_bytes, &total);
+  if (rc == KVC_OK) *scratch_bytes = total;
+  return rc;
+}
+
+int kvc_colsum_score(const kvc_colsum_params_t* params, const kvc_colsum_layer_t* layers,
+                     int num_layers, void* scratch, size_t scratch_bytes, kvc_stream_t stream) {
+  return kvc::colsum_score_impl(params, layers, num_layers, static_cast<char*>(scratch),
+                                scratch_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 int kvc_attn_accumulate(const kvc_attn_params_t* params, const kvc_attn_layer_t* layers,

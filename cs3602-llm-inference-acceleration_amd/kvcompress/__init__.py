@@ -10,6 +10,7 @@ from .benchmark import (benchmark, measure_generation_metrics, print_benchmark_s
 from .evaluate import compare_methods, evaluate_baseline, evaluate_with_compression
 from .methods import (COMPRESS_METHODS, fix_size_l2_compress, get_compress_fn, l2_compress,
                       list_methods, register_method, streaming_llm_compress)
+from .methods.colsum import attention_column_sums  # extension: H2O scores from Q and K (§7)
 from .methods.snapkv import (observation_scores, snapkv_compress,  # extension: SnapKV (§7)
                              snapkv_compress_paged)
 from .paged import PagedDest, PagedKV, compress_paged  # extension: paged caches

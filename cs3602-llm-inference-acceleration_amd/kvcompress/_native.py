@@ -90,6 +90,14 @@ OBSERVE_LAYER_DTYPE = np.dtype([("q", "<u8"), ("q_stride", "<i8", (3,)), ("reser
 assert OBSERVE_LAYER_DTYPE.itemsize == 40
 OBS_POOL_AVG, OBS_POOL_MAX = 0, 1  # enum kvc_observe_pool
 
+# struct kvc_colsum_layer (include/kvc.h: causal attention column sums) -- 112 bytes
+COLSUM_LAYER_DTYPE = np.dtype([
+    ("k", "<u8"), ("k_stride", "<i8", (3,)), ("q", "<u8"), ("q_stride", "<i8", (3,)),
+    ("lse", "<u8"), ("out_f32", "<u8"), ("out_dt", "<u8"), ("out_stride", "<i8"),
+    ("seq_len", "<i4"), ("q_len", "<i4"), ("reserved", "<i8"),
+])
+assert COLSUM_LAYER_DTYPE.itemsize == 112
+
 # struct kvc_attn_layer / kvc_hh_layer (include/kvc.h: h2o_attention heavy hitters)
 ATTN_LAYER_DTYPE = np.dtype([
     ("attn", "<u8"), ("attn_stride", "<i8", (3,)), ("acc_old", "<u8"), ("acc_new", "<u8"),
@@ -124,6 +132,12 @@ class ObserveParams(ctypes.Structure):
                 ("scores_row_stride", ctypes.c_int64)]
 
 
+class ColsumParams(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("batch", ctypes.c_int32), ("heads", ctypes.c_int32),
+                ("q_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("reserved", ctypes.c_int32 * 2)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("norm_offset", ctypes.c_size_t),
                 ("index_offset", ctypes.c_size_t), ("workspace_bytes", ctypes.c_size_t),
@@ -139,7 +153,7 @@ EXPORTS = ("kvc_version", "kvc_layer_struct_size", "kvc_max_zone_len", "kvc_stat
            "kvc_plan_paged", "kvc_launch_paged", "kvc_plan_ragged", "kvc_launch_ragged",
            "kvc_plan_scaled", "kvc_launch_scaled", "kvc_plan_repage", "kvc_launch_repage",
            "kvc_observe_plan", "kvc_observe_score", "kvc_observe_plan_paged",
-           "kvc_observe_score_paged")
+           "kvc_observe_score_paged", "kvc_colsum_plan", "kvc_colsum_score")
 
 _lib = None
 
@@ -223,6 +237,13 @@ def lib():
         L.kvc_observe_score_paged.argtypes = [ctypes.POINTER(Params),
                                               ctypes.POINTER(ObserveParams), vp, vp, vp, i32, vp,
                                               ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    if hasattr(L, "kvc_colsum_plan"):  # additive within ABI 4, like the observe entries
+        L.kvc_colsum_plan.restype = i32
+        L.kvc_colsum_plan.argtypes = [ctypes.POINTER(ColsumParams), vp, i32,
+                                      ctypes.POINTER(ctypes.c_size_t)]
+        L.kvc_colsum_score.restype = i32
+        L.kvc_colsum_score.argtypes = [ctypes.POINTER(ColsumParams), vp, i32, vp, ctypes.c_size_t,
+                                       vp]
     L.kvc_compress.restype = i32
     L.kvc_compress.argtypes = [ctypes.POINTER(Params), vp, i32, vp, ctypes.c_size_t, vp]
     L.kvc_attn_accumulate.restype = i32
@@ -470,6 +491,30 @@ def observe_score_paged(params, oparams, table, otable, pages, ws_ptr, ws_bytes,
                                          _opt(pages, PAGES_DTYPE, len(table)), len(table), ws_ptr,
                                          ws_bytes, scratch_ptr, scratch_bytes, f32_ptr,
                                          stream_ptr)
+
+
+def _need_colsum_entries():
+    if not hasattr(lib(), "kvc_colsum_plan"):
+        raise NativeLibraryError(f"{LIB_PATH} has no kvc_colsum_plan / kvc_colsum_score (built "
+                                 "before attention column sums); they need the current library")
+
+
+def colsum_plan(params, table):
+    """kvc_colsum_plan: (rc, scratch bytes).  `table` is a COLSUM_LAYER_DTYPE array."""
+    assert table.dtype == COLSUM_LAYER_DTYPE
+    _need_colsum_entries()
+    n = ctypes.c_size_t()
+    rc = lib().kvc_colsum_plan(ctypes.byref(params), table.ctypes.data, len(table),
+                               ctypes.byref(n))
+    return rc, n.value
+
+
+def colsum_score(params, table, scratch_ptr, scratch_bytes, stream_ptr):
+    """kvc_colsum_score: fills every layer's out_f32 / out_dt rows."""
+    assert table.dtype == COLSUM_LAYER_DTYPE
+    _need_colsum_entries()
+    return lib().kvc_colsum_score(ctypes.byref(params), table.ctypes.data, len(table),
+                                  scratch_ptr, scratch_bytes, stream_ptr)
 
 
 class Tables:

@@ -156,6 +156,38 @@ class H2OAttentionManager:
                 for (li, _, _, _), acc in zip(jobs, accs):
                     self.accumulated_attention[li] = acc
 
+    def update_from_queries(self, queries, keys, skip_layers: List[int] = [], lse=None):
+        """update_attention_scores without attention tensors (extension): `queries` holds per
+        layer the post-RoPE queries [B, Hq, q, D] of the last q positions (or None), `keys` the
+        kv list -- (K, V) pairs or K tensors -- after those positions were appended, `lse`
+        optionally per layer the [B, Hq, q] log-sum-exp a flash-attention forward returned.  The
+        causal attention column sums (kvc_colsum_score; bfloat16 / float16 GPU tensors), rounded
+        to K's dtype, go through update_attention_scores as [B, Hq, 1, L] attentions: decay,
+        zero-extension, reset, current_seq_len and errors are that method's.  Everything is
+        checked before a kernel runs or the manager's state moves."""
+        from .colsum import _check_layer, column_sums
+        if queries is None:
+            return
+        ks = [kv[0] if isinstance(kv, (tuple, list)) else kv for kv in keys]
+        if len(queries) != len(ks) or (lse is not None and len(lse) != len(ks)):
+            raise ValueError(f"update_from_queries: {len(queries)} query entries"
+                             + (f", {len(lse)} lse entries" if lse is not None else "")
+                             + f" for {len(ks)} layers")
+        live = [i for i, q in enumerate(queries) if q is not None and i not in skip_layers]
+        groups = {}
+        for i in live:  # one launch set per (device, dtype, shape) group; most callers have one
+            shape = _check_layer(i, ks[i], queries[i], lse[i] if lse is not None else None)
+            _check_gpu(ks[i], f"keys of layer {i}")
+            groups.setdefault((ks[i].device, ks[i].dtype) + shape[:4], []).append(i)
+        sums = [None] * len(ks)
+        for idx in groups.values():
+            _, dts = column_sums([ks[i] for i in idx], [queries[i] for i in idx],
+                                 [lse[i] if lse is not None else None for i in idx], None,
+                                 False, True)
+            for i, t in zip(idx, dts):
+                sums[i] = t[:, :, None]
+        self.update_attention_scores(sums, skip_layers)
+
     def _hh_row(self, layer_idx, seq_len):
         """(acc, m0, m, k) of a layer's heavy-hitter selection (h2o_attention.py:183-206), or
         None when the middle region is empty."""

@@ -743,6 +743,88 @@ int kvc_observe_score_paged(const kvc_params_t* params, const kvc_observe_params
                             size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                             float* scores_f32, kvc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Causal attention column sums (H2O scores without an attention tensor; additive within ABI 4: no
+ * existing struct, size or entry changes; a library without these two entries does not export
+ * them).
+ *
+ * kvc_colsum_score computes what update_attention_scores' attn.sum(dim=2) would give for the last
+ * q query positions of every layer, 1 <= q <= L, without the [B, Hq, q, L] attention tensor: the
+ * kernels read K [batch, heads, L, head_dim] twice (once with `lse`) and Q [batch, q_heads, q,
+ * head_dim], the post-RoPE queries of positions L-q .. L-1.  In fp32 (q_heads = G * heads; query
+ * head h*G + g reads KV head h):
+ *     s[i,j]      = scale * sum_d Q[b,hq,i,d] * K[b,hq/G,j,d]         j in [0, L)
+ *     allowed     : j <= L - q + i                                    (causal)
+ *     p[i,j]      = softmax of s[i,:] over the allowed j
+ *     imp[b,hq,j] = sum_i p[i,j]                                      j in [0, L)
+ * imp is per QUERY head (H2OAttentionManager keeps [B, H_attn, len] and sums heads later).  Row
+ * b*q_heads + hq of a layer's result starts out_stride elements after the row before; it is stored
+ * as fp32 to out_f32, and / or rounded once to nearest even to the call's dtype to out_dt (the
+ * bits of out_f32 rounded: the two agree bit for bit).  At least one of the two is non-NULL.
+ * Deterministic (every sum has one fixed order, no atomics: the same call gives the same bits, and
+ * a layer's bits do not depend on the layers beside it), numerical, not bit-exact against any
+ * reference -- like the observation-window contract.  Non-finite K or Q give unspecified sums and
+ * nothing else: no loop bound or address depends on data.
+ *
+ * lse (optional): fp32 [batch, q_heads, q] contiguous, the NATURAL-log-sum-exp of the scaled,
+ * masked logits of every query row -- what a flash-attention forward returns.  With it the
+ * statistics pass does not run and the sums are sum_i exp(s[i,j] - lse[i]).  Per layer.
+ *
+ * Rules (all checked by kvc_colsum_plan, a pure host function).  dtype is KVC_BF16 or KVC_F16, for
+ * Q and K alike (else KVC_E_DTYPE: fp32 and fp8 have no matrix path here); head_dim is 64, 80, 128
+ * or 256 (KVC_E_HEADDIM); batch, heads >= 1, q_heads = G * heads with G an integer in [1, 16],
+ * scale finite (0 = the default 1/sqrt(head_dim)), reserved fields 0, every layer 1 <= q_len <=
+ * seq_len <= 2^20, out_stride >= seq_len, k, q and one of out_f32 / out_dt non-NULL (KVC_E_ARG).
+ * k and q are 16-byte aligned, the strides of K's and Q's dims larger than 1 are multiples of 16
+ * bytes, last dims contiguous; lse and out_f32 4-byte, out_dt 2-byte aligned (KVC_E_ALIGN).  Paged,
+ * ragged, scaled and fp8 sources have no entry.
+ *
+ * Scratch (device memory, 16-byte aligned, no initialisation; free again when the kernels have
+ * run), summed over the layers WITHOUT lse, with R = batch * q_heads:
+ *     lse       round_up(4 * R * q, 256) bytes
+ *     partials  1024 * R * nqb * nsplit bytes: 4 waves x 32 rows x (max, sum) per query block and
+ *               key split, where  mb = 1 (q <= 32), 2 (q <= 64), else 4;  nqb = ceil(q / (32 mb));
+ *               tiles = ceil(L / 128);  want = clamp(ceil(1024 / (R nqb)), 1, min(32, ceil(tiles /
+ *               4)));  tps = ceil(tiles / want);  nsplit = ceil(tiles / tps)
+ * -- O(R * q) floats and at most 32 partial sets per query block; nothing scales with q * L.
+ *
+ * Launch discipline: per chunk of 32 layers the statistics, the lse merge (both skipped when every
+ * layer of the chunk has lse) and the column-sum kernel, every table by value in the kernel
+ * arguments; no allocation, synchronisation or global state.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct kvc_colsum_layer {
+  const void* k;       /* [batch, heads, seq_len, head_dim] of the call's dtype          */
+  int64_t k_stride[3]; /* element strides of dims batch, heads, seq                      */
+  const void* q;       /* [batch, q_heads, q_len, head_dim] of the call's dtype          */
+  int64_t q_stride[3]; /* element strides of dims batch, q_heads, q                      */
+  const float* lse;    /* optional [batch, q_heads, q_len] contiguous, natural log       */
+  float* out_f32;      /* optional fp32 rows                                             */
+  void* out_dt;        /* optional rows of the call's dtype                              */
+  int64_t out_stride;  /* elements between the rows of out_f32 / out_dt, >= seq_len      */
+  int32_t seq_len;     /* L                                                              */
+  int32_t q_len;       /* q                                                              */
+  int64_t reserved;    /* 0                                                              */
+} kvc_colsum_layer_t;  /* 112 bytes */
+
+typedef struct kvc_colsum_params {
+  int32_t dtype;       /* enum kvc_dtype: KVC_BF16 or KVC_F16 */
+  int32_t batch;
+  int32_t heads;       /* KV heads                            */
+  int32_t q_heads;     /* G * heads                           */
+  int32_t head_dim;
+  float scale;         /* softmax scale; 0 = 1/sqrt(head_dim) */
+  int32_t reserved[2]; /* 0                                   */
+} kvc_colsum_params_t; /* 32 bytes */
+
+/* Validates the rules above and reports the scratch kvc_colsum_score needs.  Pure host function. */
+int kvc_colsum_plan(const kvc_colsum_params_t* params, const kvc_colsum_layer_t* layers,
+                    int num_layers, size_t* scratch_bytes);
+
+/* Re-validates and enqueues the kernel set on `stream`.  `scratch` is at least kvc_colsum_plan's
+ * scratch_bytes (KVC_E_WORKSPACE; it may be NULL when that is 0). */
+int kvc_colsum_score(const kvc_colsum_params_t* params, const kvc_colsum_layer_t* layers,
+                     int num_layers, void* scratch, size_t scratch_bytes, kvc_stream_t stream);
+
 /* Diagnostic entry (tests of the device status channel; no reference counterpart).  Runs the
  * 512-thread SELECT (params->phases == KVC_PHASE_SELECT) or SELECT_GATHER (KVC_PHASE_SELECT |
  * KVC_PHASE_GATHER) kernel of a planned table (at most 64 layers) as kvc_launch would, but with
